@@ -10,7 +10,17 @@ a gloo barrier brackets the timed region and the max time over ranks is reported
 config 3 (B = 4096, seed 45); N ranks run config 5 (one global batch of N x 4096, seed 47, a
 contiguous shard per rank).  `--gpus N` without a launcher starts the N ranks itself.
 
+A plain run does only what `value` needs: set up, warm up, time the K steps, print the line
+(metric, value, unit, ms_per_step, the configuration and the iteration counts of the last step).
+`--dump-outputs DIR` also writes what the last timed step returned (XU and the per-problem
+statistics of i7m_solve_device) as DIR/<name>.npy; the inputs are seeded, so two builds run with
+the same arguments can be compared array for array.  `--full` adds everything else to the line:
+the event pass (p50, per-kernel times, rooflines), the B = 1 and host-to-host latencies, the exact
+mode, the parities against the C++ port, the CPU baselines, the closed loop, configs 2 and 4
+(the --no-* switches and --exact-steps, --config4-steps, --cpu-*, --latency-reps shape that part).
+
     python bench.py [--gpus N [--share-devices]] [--steps K] [--warmup W] [--batch B] [--N 32]
+                    [--dump-outputs DIR] [--full]
 """
 from __future__ import annotations
 
@@ -358,12 +368,13 @@ def mpc_closed_loop(model, stream, local: int, B: int = 4096, N: int = 32, steps
             "instances_alive_at_end": int(np.isfinite(d[-1]).sum()), "finite": bool(np.isfinite(q[np.isfinite(q)]).all())}
 
 
-def gather_rank_rows(dist, device: int, elapsed_s: float, h2h_solves_per_s: float):
+def gather_rank_rows(dist, device: int, elapsed_s: float, h2h_solves_per_s=None):
     """[device, own pass-1 elapsed, own host-to-host rate] of every rank, in rank order (gloo
-    all_gather; `dist` None = one rank)."""
+    all_gather; `dist` None = one rank).  The rate is NaN where it was not measured (a run
+    without --full)."""
     import torch
 
-    row = [float(device), float(elapsed_s), float(h2h_solves_per_s)]
+    row = [float(device), float(elapsed_s), float("nan") if h2h_solves_per_s is None else float(h2h_solves_per_s)]
     if dist is None:
         return [row]
     parts = [torch.zeros(3, dtype=torch.float64) for _ in range(dist.get_world_size())]
@@ -378,7 +389,7 @@ def per_rank_summary(rows, B: int, steps: int):
     els = [r[1] for r in rows]
     return {"elapsed_s": {"min": min(els), "median": statistics.median(els), "max": max(els)},
             "ranks": [{"rank": i, "device": int(r[0]), "elapsed_s": r[1], "solves_per_s": B * steps / r[1],
-                       "host_to_host_solves_per_s": r[2]} for i, r in enumerate(rows)],
+                       **({} if r[2] != r[2] else {"host_to_host_solves_per_s": r[2]})} for i, r in enumerate(rows)],
             "note": "elapsed_s: each rank's own barrier-to-barrier time of pass 1 (value uses the max over ranks); "
                     "host_to_host_solves_per_s: each rank's median host-to-host call, all ranks copying at once"}
 
@@ -708,10 +719,11 @@ def exact_mode(model, local, B, N, xcur, goals, XU, stream, steps, warmup, world
     return res
 
 
-def headline_line(*, value, elapsed, steps, warmup, world, B, N, seed, devs, step_ms, ktimes, roofline,
-                  osqp_iters, qp_iters_mean, el_ev, lat_b1_ms=None, h2h_s=None, rank_rows=None):
-    """The ONE JSON line's top level (the headline ADMM leg), from measured numbers; rank 0 adds the
-    parity, CPU baseline and extra objects.  Separate from main() so its keys are testable on CPU
+def headline_line(*, value, elapsed, steps, warmup, world, B, N, seed, devs, osqp_iters, qp_iters_mean,
+                  step_ms=None, ktimes=None, roofline=None, el_ev=None, lat_b1_ms=None, h2h_s=None, rank_rows=None):
+    """The ONE JSON line's top level (the headline ADMM leg), from measured numbers; with --full
+    the event pass's keys (step_ms, ktimes, roofline, el_ev given) and, on rank 0, the parity, CPU
+    baseline and extra objects.  Separate from main() so its keys are testable on CPU
     (tests/test_sharding.py, world size 2 under gloo)."""
     out = {
         "metric": "SQP-MPC solves/sec (Indy7 6-DOF, N=32)",
@@ -746,20 +758,23 @@ def headline_line(*, value, elapsed, steps, warmup, world, B, N, seed, devs, ste
                                        "value'); BASELINE.md 4's host-to-host rate (H2D + solve + D2H, median of 20 "
                                        "calls after 3 warm-up) is host_to_host_solves_per_s, its p50 "
                                        "p50_latency_h2h_ms; the exact KKT mode is the extra exact_mode"},
-        "p50_latency_ms": statistics.median(step_ms),
-        "p50_latency_definition": "p50_latency_ms: device time per batched step (HIP events on the solve stream, the "
-                                  "OSQP reset included); p50_latency_h2h_ms: BASELINE.md 4's p50 of the host-to-host "
-                                  "batched call; p50_latency_b1_ms: host-to-host B = 1 call (device-resident input)",
-        "kernel_timing": {"pass": "second pass of the same K steps with per-launch HIP events on each kernel's dispatch",
-                          "value_during_event_pass": B * world * steps / el_ev},
         "qp_iters_mean": qp_iters_mean,
         "osqp_iters_per_qp": osqp_iters,
-        "kernels": kernel_summary(ktimes),
-        "roofline": roofline,
         "roofline_solve": {"bound": "hbm", "achieved": value * algorithmic_bytes(N) / 1e9, "peak": HBM_PEAK_GBS * world,
                            "unit": "GB/s", "frac": value * algorithmic_bytes(N) / 1e9 / (HBM_PEAK_GBS * world),
                            "bytes_per_solve": algorithmic_bytes(N)},
     }
+    if step_ms is not None:
+        out["p50_latency_ms"] = statistics.median(step_ms)
+        out["p50_latency_definition"] = (
+            "p50_latency_ms: device time per batched step (HIP events on the solve stream, the "
+            "OSQP reset included); p50_latency_h2h_ms: BASELINE.md 4's p50 of the host-to-host "
+            "batched call; p50_latency_b1_ms: host-to-host B = 1 call (device-resident input)")
+        out["kernel_timing"] = {"pass": "second pass of the same K steps with per-launch HIP events on each kernel's "
+                                        "dispatch",
+                                "value_during_event_pass": B * world * steps / el_ev}
+        out["kernels"] = kernel_summary(ktimes)
+        out["roofline"] = roofline
     if lat_b1_ms is not None:
         out["p50_latency_b1_ms"] = lat_b1_ms
     if h2h_s is not None:
@@ -777,6 +792,29 @@ def osqp_iter_summary(it):
     return {"mean": float(used.mean()), "median": float(np.median(used)), "max": int(used.max())}
 
 
+DUMP_MAX_BYTES = 48 << 20   # of XU; the statistics add under 100 B per problem
+
+
+def dump_outputs(dirname, out_xu, st):
+    """--dump-outputs: what the last timed step's i7m_solve_device returned on this rank, one
+    float64 .npy per array: xu (B, 18N - 6) and the per-problem statistics (qp_iters, n_alphas,
+    n_steps; alphas and stepsizes with the entries past n_alphas / n_steps zeroed).  A batch whose
+    XU exceeds DUMP_MAX_BYTES is written as a fixed sample of its problems (seed 0, ascending);
+    rows.npy holds the indices of the problems written."""
+    os.makedirs(dirname, exist_ok=True)
+    B = len(out_xu)
+    cap = max(1, DUMP_MAX_BYTES // (out_xu.shape[1] * 8))
+    rows = np.arange(B) if B <= cap else np.sort(np.random.default_rng(0).choice(B, cap, replace=False))
+    st = st[rows]
+    k = np.arange(st["alphas"].shape[1])[None, :]
+    arrays = {"xu": out_xu[rows], "rows": rows,
+              "qp_iters": st["qp_iters"], "n_alphas": st["n_alphas"], "n_steps": st["n_steps"],
+              "alphas": np.where(k < st["n_alphas"][:, None], st["alphas"], 0.0),
+              "stepsizes": np.where(k < st["n_steps"][:, None], st["stepsizes"], 0.0)}
+    for name, a in arrays.items():
+        np.save(os.path.join(dirname, name + ".npy"), np.ascontiguousarray(a, dtype=np.float64))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1, help="ranks = GPUs; without WORLD_SIZE in the environment "
@@ -788,6 +826,11 @@ def main():
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--batch", type=int, default=4096, help="problems per GPU")
     ap.add_argument("--N", type=int, default=32)
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step returned (XU, per-problem statistics) as DIR/<name>.npy")
+    ap.add_argument("--full", action="store_true",
+                    help="also run everything beside the headline: event pass (p50, kernels, rooflines), latencies, "
+                         "exact mode, parities, CPU baselines, closed loop, configs 2 and 4 (the options below)")
     ap.add_argument("--cpu-budget", type=float, default=20.0)
     ap.add_argument("--cpu-threads", type=int, default=cpu_threads())
     ap.add_argument("--no-cpu-baseline", action="store_true")
@@ -810,7 +853,7 @@ def main():
     if world != args.gpus:
         ap.error(f"--gpus {args.gpus} but the launcher started WORLD_SIZE={world} ranks")
     # the CPU port for this host is compiled (a child process) before anything touches the GPU
-    native = build_native_port() if (rank == 0 and world == 1 and not args.no_cpu_baseline) else None
+    native = build_native_port() if (args.full and rank == 0 and world == 1 and not args.no_cpu_baseline) else None
     import torch
     import torch.distributed as dist
 
@@ -868,6 +911,26 @@ def main():
     torch.cuda.synchronize()
     # pass 1: `value` — nothing but the steps between the barriers
     elapsed, own_el, _ = leg.timed(args.steps, world, dist, False)
+    value = B * world * args.steps / elapsed
+    st = leg.stats()
+    out_xu = leg.output()
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, out_xu, st)
+    if not args.full:
+        # a plain run: the line from pass 1 and its last step's counts, nothing else is run
+        it = leg.h.admm_stats(B)[0]
+        leg.h.close()
+        rank_rows = gather_rank_rows(dist if world > 1 else None, local, own_el)
+        line = headline_line(value=value, elapsed=elapsed, steps=args.steps, warmup=args.warmup, world=world, B=B,
+                             N=N, seed=seed, devs=[int(r[0]) for r in rank_rows], osqp_iters=osqp_iter_summary(it),
+                             qp_iters_mean=float(st["qp_iters"].mean()), rank_rows=rank_rows)
+        line["finite"] = bool(np.isfinite(out_xu).all())
+        if rank == 0:
+            print(json.dumps(line), flush=True)
+        if world > 1:
+            dist.barrier()
+            dist.destroy_process_group()
+        return
     # pass 2: the same K steps with per-step events (p50) and per-launch start/stop events on each
     # kernel's dispatch (hipExtLaunchKernelGGL): per-kernel durations for the roofline
     el_ev, _, step_ms = leg.timed(args.steps, world, dist, True)
@@ -879,7 +942,6 @@ def main():
     h2h_s = leg.host_to_host(xcur, goals, XU)
     rank_rows = gather_rank_rows(dist if world > 1 else None, local, own_el, B / h2h_s)
     devs = [int(r[0]) for r in rank_rows]
-    value = B * world * args.steps / elapsed
     roof = admm_roofline(ktimes, args.steps, it, B, N, elapsed / args.steps)
     line = headline_line(value=value, elapsed=elapsed, steps=args.steps, warmup=args.warmup, world=world, B=B, N=N,
                          seed=seed, devs=devs, step_ms=step_ms, ktimes=ktimes, roofline=roof,

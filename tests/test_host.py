@@ -11,7 +11,7 @@ from indy7_mpc_amd.sharding import shard_range, shard_ranges
 from oracle import rbd
 from oracle.osqp_ref import OSQPSolverRef, synthetic_batch
 
-URDF = "/root/reference/description/indy7.urdf"
+URDF = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "indy7.urdf")  # the robot description, a stored fixture
 
 
 def test_model_surface(model):
@@ -23,7 +23,6 @@ def test_model_surface(model):
     assert len(d.oMi) == model.njoints
 
 
-@pytest.mark.skipif(not os.path.exists(URDF), reason="reference URDF only in the build container")
 def test_urdf_parse_matches_committed_params():
     p = parse_urdf(URDF)
     assert np.array_equal(RobotModel(p).packed(), default_model().packed())
@@ -130,3 +129,51 @@ def test_bench_refuses_more_ranks_than_devices():
                        capture_output=True, text=True, timeout=300, cwd=root)
     assert r.returncode == 2, (r.returncode, r.stderr[-2000:])
     assert "--share-devices" in r.stderr
+
+
+def test_bench_plain_line_keys():
+    """A run without --full has only pass 1: the line keeps metric, value, unit, dtype and
+    ms_per_step as they are and carries none of the event pass's keys."""
+    import bench
+
+    it = np.full((8, 8), -1, dtype=np.int32)
+    it[:, 0] = 25
+    line = bench.headline_line(value=8 * 5 / 0.25, elapsed=0.25, steps=5, warmup=2, world=1, B=8, N=32, seed=45,
+                               devs=[0], osqp_iters=bench.osqp_iter_summary(it), qp_iters_mean=1.0)
+    assert line["metric"] == "SQP-MPC solves/sec (Indy7 6-DOF, N=32)" and line["unit"] == "solves/s"
+    assert line["higher_is_better"] is True and line["dtype"] == "f64"
+    assert line["value"] == pytest.approx(160.0) and line["ms_per_step"] == pytest.approx(50.0)
+    assert line["steps"] == 5 and line["warmup"] == 2 and line["config"]["qp_mode"] == "admm"
+    assert not {"kernels", "roofline", "p50_latency_ms", "kernel_timing", "per_rank"} & set(line)
+    rows = bench.gather_rank_rows(None, 0, 0.25)
+    assert set(bench.per_rank_summary(rows, 8, 5)["ranks"][0]) == {"rank", "device", "elapsed_s", "solves_per_s"}
+
+
+def test_bench_dump_outputs(tmp_path, monkeypatch):
+    """--dump-outputs: float64 .npy files of XU and the statistics, entries past the used counts
+    zeroed; a batch over the size cap is written as the same seeded sample every time."""
+    import bench
+    from indy7_mpc_amd import _lib
+
+    B, T = 6, 18 * 4 - 6
+    xu = np.random.default_rng(3).normal(size=(B, T))
+    st = np.zeros(B, dtype=_lib.STATS_DTYPE)
+    st["qp_iters"], st["n_alphas"], st["n_steps"] = 2, 1, 2
+    st["alphas"][:] = 0.5
+    st["stepsizes"][:] = 3.0
+    bench.dump_outputs(str(tmp_path / "a"), xu, st)
+    got = {n[:-4]: np.load(tmp_path / "a" / n) for n in os.listdir(tmp_path / "a")}
+    assert set(got) == {"xu", "rows", "qp_iters", "n_alphas", "n_steps", "alphas", "stepsizes"}
+    assert all(a.dtype == np.float64 for a in got.values())
+    np.testing.assert_array_equal(got["xu"], xu)
+    np.testing.assert_array_equal(got["rows"], np.arange(B))
+    assert (got["alphas"][:, 0] == 0.5).all() and not got["alphas"][:, 1:].any()
+    assert (got["stepsizes"][:, :2] == 3.0).all() and not got["stepsizes"][:, 2:].any()
+    monkeypatch.setattr(bench, "DUMP_MAX_BYTES", 4 * T * 8)
+    bench.dump_outputs(str(tmp_path / "b"), xu, st)
+    bench.dump_outputs(str(tmp_path / "c"), xu, st)
+    rows = np.load(tmp_path / "b" / "rows.npy").astype(int)
+    assert len(rows) == 4 and (np.diff(rows) > 0).all()
+    np.testing.assert_array_equal(rows, np.load(tmp_path / "c" / "rows.npy"))
+    np.testing.assert_array_equal(np.load(tmp_path / "b" / "xu.npy"), xu[rows])
+    assert len(np.load(tmp_path / "b" / "qp_iters.npy")) == 4

@@ -14,7 +14,6 @@ for B in (1, 64):
     r = run(B, 32, {})
     print(os.environ['I7M_LIB'].split('/')[-1], 'B=%d' % B, r['kernels_us'], 'p50_ms', round(r['p50_ms'], 4))
 PY
-  I7M_LIB=$PWD/$L timeout -k 10 120 python bench.py --no-cpu-baseline --no-config4 --no-config2 --steps 20 > gpurun_out/b.json 2>/dev/null || exit 3
-  python -c "
-import json; d=json.load(open('gpurun_out/b.json')); print('  B=4096', round(d['value']), {k:round(v['avg_us'],1) for k,v in d['kernels'].items()})"
+  I7M_LIB=$PWD/$L timeout -k 10 120 python bench.py --full --no-cpu-baseline --no-config4 --no-config2 --steps 20 2>/dev/null | python -c "
+import json, sys; d=json.loads(sys.stdin.read().strip().splitlines()[-1]); print('  B=4096', round(d['value']), {k:round(v['avg_us'],1) for k,v in d['kernels'].items()})" || exit 3
 done

@@ -15,18 +15,18 @@ if has tests; then
   tail -3 $O/pytest_gpu.log
 fi
 if has bench; then
-  timeout -k 10 600 python bench.py > $O/bench.json 2> $O/bench.err || { tail -20 $O/bench.err; exit 2; }
+  timeout -k 10 600 python bench.py --full > $O/bench.json 2> $O/bench.err || { tail -20 $O/bench.err; exit 2; }
   cat $O/bench.json
 fi
 if has multi; then
   # bench.py --gpus 2 starting its own ranks, both on the one GPU (--share-devices rehearsal)
-  timeout -k 10 300 python bench.py --gpus 2 --share-devices --steps 20 > $O/bench_g2.json 2> $O/bench_g2.err || { tail -20 $O/bench_g2.err; exit 13; }
+  timeout -k 10 300 python bench.py --full --gpus 2 --share-devices --steps 20 > $O/bench_g2.json 2> $O/bench_g2.err || { tail -20 $O/bench_g2.err; exit 13; }
   cat $O/bench_g2.json
 fi
 cd /tmp
 if has trace; then
   # the bench's own GPU work under the kernel tracer (no CPU leg / extras, to keep it short)
-  timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $O/trace -o run -- python $R/bench.py --no-cpu-baseline --no-config4 --no-config2 > $O/trace.log 2>&1 || { tail -20 $O/trace.log; exit 3; }
+  timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $O/trace -o run -- python $R/bench.py --full --no-cpu-baseline --no-config4 --no-config2 > $O/trace.log 2>&1 || { tail -20 $O/trace.log; exit 3; }
   python $R/tools/trace_summary.py $O/trace/run_kernel_trace.csv --batch 4096 > $O/trace_summary.json
 fi
 if has pmc; then
