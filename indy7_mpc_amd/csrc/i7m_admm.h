@@ -72,9 +72,6 @@ struct AdmmArgs {
 #ifndef I7M_ADMM_FSTRIDE
 #define I7M_ADMM_FSTRIDE 19  // the register factor's LDS row stride for S and C (18: 3-way bank conflicts on row reads)
 #endif
-#ifndef I7M_ADMM_FACTOR
-#define I7M_ADMM_FACTOR 2  // 2: register Cholesky (adm_factor), 1: LDS-staged (adm_factor_lds)
-#endif
 #ifndef I7M_ADMM_SCALE_WPE
 #define I7M_ADMM_SCALE_WPE 2  // (N <= 32: the linearisation magnitudes stay in registers for all ten passes)
 #endif
@@ -802,82 +799,6 @@ __device__ __forceinline__ void adm_factor(const AdmmArgs& a, int N, double rho,
 #endif
 }
 
-// The factor with every step's operands through LDS (the kernel before the register Cholesky;
-// I7M_ADMM_FACTOR 1, A/B builds)
-__device__ void adm_factor_lds(const AdmmArgs& a, int N, double rho, const double* Pq, const double* Pd, const double* Ib,
-                           double* Rb, double* sS, double* sJ, double* sL, double* sCp,
-                           int l) {
-  const double re = 1e3 * rho, sigma = a.A.sigma;
-  for (int k = 0; k < N; ++k) {
-    const int nk = k < N - 1 ? 18 : 12;
-    if (k < N - 1) adm_stage_J(sJ, Rb + ADM_REC * k + REC_J, l);
-    wave_sync();
-    for (int e = l; e < 324; e += 64) {
-      const int i = e / 18, j = e - 18 * i;
-      double v = 0.0;
-      if (i < nk && j < nk) {
-        if (i < 6 && j < 6) v = Pq[36 * k + 6 * i + j];
-        else if (i == j && i >= 6) v = Pd[18 * k + i];
-        if (i == j) v += sigma;
-        if (i == j && i < 12) v += re * (Ib[12 * k + i] * Ib[12 * k + i]);
-        if (k < N - 1) {
-          double acc = 0.0;
-          for (int r = 0; r < 12; ++r) acc += sJ[18 * r + i] * sJ[18 * r + j];
-          v += re * acc;
-        }
-        if (k > 0 && i < 12 && j < 12) {
-          double acc = 0.0;
-          for (int q = 0; q < 18; ++q) acc += sCp[18 * i + q] * sCp[18 * j + q];
-          v -= acc;
-        }
-      }
-      sS[e] = v;
-    }
-    wave_sync();
-    // right-looking Cholesky
-    for (int p = 0; p < nk; ++p) {
-      const double d = sqrt(sS[18 * p + p]);
-      const double id = 1.0 / d;
-      wave_sync();
-      if (l == 0) sS[18 * p + p] = d;
-      if (l > p && l < nk) sS[18 * l + p] = sS[18 * l + p] * id;
-      wave_sync();
-      for (int e = l; e < 324; e += 64) {
-        const int i = e / 18, j = e - 18 * i;
-        if (j > p && i >= j && i < nk) sS[e] = sS[e] - sS[18 * i + p] * sS[18 * j + p];
-      }
-      wave_sync();
-    }
-    // inverse of the lower factor, one column per lane
-    for (int e = l; e < 324; e += 64) sL[e] = 0.0;
-    wave_sync();
-    if (l < nk) {
-      const int j = l;
-      sL[18 * j + j] = 1.0 / sS[18 * j + j];
-      for (int i = j + 1; i < nk; ++i) {
-        double acc = 0.0;
-        for (int q = j; q < i; ++q) acc += sS[18 * i + q] * sL[18 * q + j];
-        sL[18 * i + j] = -acc / sS[18 * i + i];
-      }
-    }
-    wave_sync();
-    for (int e = l; e < 324; e += 64) {
-      const int i = e / 18, j = e - 18 * i;
-      if (j < adm_lw(i)) Rb[ADM_REC * k + adm_lrec(i, j)] = sL[e];
-    }
-    if (k < N - 1) {
-      for (int e = l; e < 216; e += 64) {
-        const int i = e / 18, j = e - 18 * i;
-        double acc = 0.0;
-        for (int q = 0; q <= j; ++q) acc += sJ[18 * i + q] * sL[18 * j + q];
-        const double cv = re * Ib[12 * (k + 1) + i] * acc;
-        sCp[e] = cv;
-      }
-    }
-    wave_sync_all();
-  }
-}
-
 // k_admm_scale (PH 1: scaling, the new q and l; c to a.cs) and k_admm_factor (PH 8: the block
 // Cholesky), one problem per wave; each compiled for its own registers and LDS.
 template <int PH, int CT>
@@ -913,11 +834,7 @@ __device__ __forceinline__ void admm_body(const AdmmArgs& a) {
     if (l == 0) a.cs[b] = c;
   }
   if constexpr (PH & 8) {
-#if I7M_ADMM_FACTOR == 1
-    adm_factor_lds(a, N, a.srho[b], Pq, Pd, Ib, Rb, sS, sJ, sL, sCp, l);
-#else
     adm_factor(a, N, a.srho[b], Pq, Pd, Ib, Rb, sS, sJ, sL, sCp, sStg, l);
-#endif
   }
 }
 

@@ -24,6 +24,7 @@
 #include "i7m_box.h"
 #include "i7m_admm.h"
 #include "i7m_mpc.h"
+#include "i7m_plan.h"
 
 // Source hash of the tree this library was built from (__graft_entry__.build passes it), so
 // tests and smoke() can check that the loaded binary matches the sources they run against.
@@ -56,6 +57,7 @@ hipError_t i7m_launch_sqp_fused(bool spec, int W, bool fext_world, int it, hipSt
 hipError_t i7m_prepare_sqp_fused(int dev, int N);
 
 static_assert(sizeof(i7m_problem_stats) == sizeof(ProblemStats), "stats layout");
+static_assert(ADMM_RES_MAX_N == ARES_N, "i7m_plan.h: k_admm_iter_res's horizon");
 
 namespace {
 
@@ -80,17 +82,6 @@ struct Timing {
 
 }  // namespace
 
-// k_riccati_mfma's Gauss-Jordan pivot broadcasts switch from v_readlane to DPP from this batch
-// size on (riccati_mfma_body BC)
-// DPP pivot broadcasts at every batch size since the round-3 stage changes (re-measured: 57.9 -> 54.7 us
-// at B = 1024, 44.3 -> 42.6 at 512, 41.4 -> 40.0 at 64, 40.7 -> 39.5 at B = 1; before them they
-// cost ~4.5 us below 2048; profiles/r03_ric_bc_retune_ab.txt)
-constexpr int RIC_DPP_MIN_B = 0;
-constexpr int RIC_W2_MAX_B = 128;     // two-wave Riccati up to this batch size (I7M_RIC_W2 forces): 43.9 -> 42.0 us at B = 1, 44.6 -> 42.7 at 64; slower from 512
-// wave priority by progress once Riccati waves share SIMDs: from 768 problems (re-measured in round 3:
-// 55.2 -> 52.4 us at B = 768, 42.5 -> 43.3 at 512; profiles/r03_ric_bc_retune_ab.txt)
-constexpr int RIC_PRIO_MIN_B = 768;
-
 struct i7m_handle {
   i7m_config cfg;
   int dev = 0;
@@ -112,9 +103,6 @@ struct i7m_handle {
   // I7M_QP_ADMM (i7m_admm.h): one allocation, per-problem OSQP state and k_admm scratch
   double* d_admm = nullptr;
   int* d_admm_it = nullptr;  // 2 x (max_batch, I7M_MAX_SQP): OSQP iterations, then OSQP status, per SQP iteration
-  // box QP: 1 k_ipm_fused<false> (default), 0 I7M_IPM=delta (k_ipm_fused<true>: the corrector
-  // reuses the predictor's factorisation; measured slower), 2 I7M_IPM=split
-  int ipm_mode = 1;
   int ablate = 0;                  // I7M_DIAG builds only (I7M_ABLATE): timing variants, results invalid
   bool spec = false;               // model == kIndy7Model: use the kernels with the constants baked in
   bool has_fext = false;
@@ -128,65 +116,13 @@ struct i7m_handle {
   };
   std::vector<GraphEntry> graphs;
   unsigned long long graph_clock = 0;
-  bool use_graph = false;  // I7M_GRAPH=1: capture the solve once per buffer set, replay it
-                           // (measured 4-5 us slower per solve at B = 1 and 64, level at 4096)
-  int ls_waves = 0;  // waves per problem in k_linesearch: 0 automatic (4 for B <= 768), else I7M_LS_WAVES (1, 2 or 4)
-  // I7M_LS_TAIL = r > 0: split line search — the first launch (one wave per problem) stops after r
-  // rounds, a second launch with two waves per problem finishes the unresolved problems
-  int ls_tail = 0;
+  Tuning tune;  // the launch knobs (i7m_plan.h: tuning_from_env at i7m_create)
   double* d_lsbase = nullptr;  // (max_batch) base merits handed to the second launch
   int* d_lspend = nullptr;     // (max_batch) pending flags
-  int pipeline = I7M_PIPE_AUTO;  // cfg.pipeline, or I7M_PIPE=split|fused
-  int ric_w2 = -1;               // k_riccati_mfma_w2 (two waves per problem): 1 / 0, -1 = by batch size
-  int ric_bc = -1;               // k_riccati_mfma broadcast variant (BC bits), -1 = by batch size
-  // host-to-host i7m_solve split into chunks on two streams, so the copies of one chunk overlap
-  // the solve of another (0 = one piece on h->stream; I7M_H2H_CHUNKS or cfg.h2h_chunks)
-  int h2h_chunks = 0;
-  int admm_chunk = 0;  // I7M_ADMM_CHUNK: k_admm launched over this many problems at a time (0: all)
-  int dev_ranges = 0;  // I7M_DEV_RANGES: i7m_solve_device in this many ranges on the two chunk streams (A/B)
-  // ADMM mode, i7m_solve_device with B >= admm_stagger_min_b: the batch as admm_ranges ranges on
-  // streams of their own, each started once the one before has passed a mark (1: its first QP's
-  // scaling and factor; 2: its first QP; A/B: 3 its first linearisation, 4 its first scaling), so one range's latency-bound phases (the factor, the
-  // OSQP iterations after the first termination check) overlap another's stream-bound ones
-  // (DESIGN.md §4.7).  0: one range.  I7M_ADMM_STAGGER, I7M_ADMM_RANGES, I7M_ADMM_STAGGER_MIN_B.
-  int admm_stagger = 1;
-  int stagger_modes = 1 << I7M_QP_ADMM;  // the QP modes that stagger (bit per mode; I7M_STAGGER_MODES)
-  int admm_ranges = 2;
-  // k_admm_iter2 (two problems per wave) for launches of at most 512 problems: 3.5 % shorter at
-  // B <= 256, level at 1 024, 19-32 % longer at 4 096 (profiles/r06p, r06q); I7M_ADMM_ITER2 = 0
-  // never, 1 always, -1 (default) by that size
-  int admm_iter2 = -1;
-  // k_admm_iter_res (one problem per workgroup, its records and vectors resident in LDS) for
-  // launches of at most admm_res_max problems at N <= ARES_N without rho adaptation; I7M_ADMM_RES
-  // = 0 never, 1 whenever it fits, -1 (default) by that size
-  int admm_res = -1;
-  int admm_res_max = 256;
-  // k_admm_scale / k_admm_factor as built under the max-ILP scheduler (i7m_admm_prep_tu.hip) for
-  // launches of at most admm_prep_ilp_max problems, else this unit's: 6 % shorter at B <= 256, but
-  // at config 3 (staggered ranges of 2048) the step 0.6 % longer beside the other range's
-  // iteration (profiles/r06zn, r06zo); I7M_ADMM_PREP_ILP = 0 never, 1 always, -1 (default) by size
-  int admm_prep_ilp = -1;
-  int admm_prep_ilp_max = 1024;
-  // extra dynamic LDS per k_admm_iter workgroup (I7M_ADMM_ITER_DYN_LDS, bytes; A/B): past 160 KB / 4
-  // it leaves one SIMD of every CU, and its LDS, to the other range's kernels
-  int admm_iter_dyn_lds = 0;
-  int admm_chains = 1;  // ranges r wait for range r - chains's mark (I7M_ADMM_CHAINS, A/B: 2 = two independent stagger chains)
-  int admm_split = 500;  // two ranges: the first's share of the batch, per mille (I7M_ADMM_SPLIT, A/B)
-  int admm_stagger_min_b = 3072;  // measured, two ranges: B = 8192 / 4096 / 3072 +9 / +17 / +5 %; 2048 / 1024 -8 / -11 %
-  static constexpr int kMaxRanges = 4;
-  hipStream_t rs[kMaxRanges] = {};  // ranges 2.. (0 and 1 run on cs[0], cs[1]); created on first use
-  hipEvent_t ev_rmark[kMaxRanges] = {}, ev_rdone[kMaxRanges] = {};
-  hipEvent_t mark_ev = nullptr;  // set: solve_qp records it at the mark, once, and clears it
+  hipEvent_t ev_rmark = nullptr;  // the staggered ranges' / chunks' mark (StaggerMark)
   hipStream_t cs[2] = {nullptr, nullptr};
   hipStream_t cs2 = nullptr;  // h2h_pipe >= 2: the second solve stream (created on first use)
   hipEvent_t ev_order = nullptr, ev_done[2] = {nullptr, nullptr};
-  // pipelined host-to-host chunks (h2h_pipe 1 / 2; I7M_H2H_PIPE=0: the first cut's two alternating
-  // streams): per chunk, copy-in on cs[0] -> solve -> copy-out on cs[1]
-  // 2 (default): the chunks' solves alternate over two streams, so one chunk's solve may overlap the
-  // next one's start; 1: all solves on the handle's stream (A/B); 3: as 2, with the
-  // copies out issued by a second host thread (pageable copies block the issuing thread)
-  int h2h_pipe = 2;
-  int h2h_taper = 1;  // I7M_H2H_TAPER=0: equal chunks (A/B)
   std::vector<hipEvent_t> ev_in, ev_cmp;
   // timing
   bool timing = false;
@@ -420,20 +356,13 @@ int launch_riccati(i7m_handle* h, hipStream_t s, const Bufs& W, const SolveParam
 #endif
     // (the diag library's default path is the release selection below, so its per-wave timelines
     // show the shipping kernels)
-    // cross-lane broadcasts (riccati_mfma_body BC): the rollout's and the pivots' by DPP (from
-    // RIC_DPP_MIN_B problems on, now every size); I7M_RIC_BC=0..3 forces one (A/B)
-    // wave priority by progress (BC bit 2) once SIMDs hold more than one wave: -6 % at B = 4096,
-    // -4 % at B = 1024 (uneven dispatch puts two waves on some SIMDs), +1 us at B = 64
-    const int bc = h->ric_bc >= 0 ? h->ric_bc
-                                  : (P.B >= RIC_DPP_MIN_B ? 3 : 2) | (P.B >= RIC_PRIO_MIN_B ? 4 : 0);
-    // small batches: two waves per problem (k_riccati_mfma_w2), the stage's MFMA chains split
-    const bool w2 = !vout && (h->ric_w2 >= 0 ? h->ric_w2 != 0 : P.B <= RIC_W2_MAX_B);
-    if (w2) {
+    const RicVariant rv = riccati_variant(h->tune, P.B, vout != nullptr);
+    if (rv.w2) {
       auto go2 = [&](auto kern) {
         hipExtLaunchKernelGGL(kern, dim3(P.B), dim3(128), 0, s, ea, eb, 0, P, xu, xs, W.lin, W.cost, W.qpd, active,
                               W.kbuf, sol);
       };
-      if (bc & 1) go2(k_riccati_mfma_w2<3>);
+      if (rv.bc & 1) go2(k_riccati_mfma_w2<3>);
       else go2(k_riccati_mfma_w2<2>);
       return;
     }
@@ -441,7 +370,7 @@ int launch_riccati(i7m_handle* h, hipStream_t s, const Bufs& W, const SolveParam
       hipExtLaunchKernelGGL(kern, dim3(P.B), dim3(64), 0, s, ea, eb, 0, P, xu, xs, W.lin, W.cost, W.qpd, active, W.kbuf,
                             sol, (const double*)nullptr, (const double*)nullptr, vout);
     };
-    switch (bc) {
+    switch (rv.bc) {
       case 1: go(k_riccati_mfma<0, false, 1>); break;
       case 2: go(k_riccati_mfma<0, false, 2>); break;
       case 3: go(k_riccati_mfma<0, false, 3>); break;
@@ -452,13 +381,14 @@ int launch_riccati(i7m_handle* h, hipStream_t s, const Bufs& W, const SolveParam
   });
 }
 
-// waves per problem of the line search (k_linesearch) and of k_sqp_fused
-// (k_linesearch: 4 waves per problem up to 768 problems — re-measured in round 3: 28.2 -> 19.0 us at
-// B = 384, 28.6 -> 19.8 at 512, 29.9 -> 28.8 at 768, 30.6 -> 35.2 at 1024, profiles/r03_ls_waves_ab.txt;
-// k_sqp_fused keeps the 256 it was measured with)
-constexpr int LS_W4_MAX_B = 768, FUSED_W4_MAX_B = 256;
-int waves_for(const i7m_handle* h, int B, int max_b4 = LS_W4_MAX_B) {
-  return h->ls_waves > 0 ? h->ls_waves : (B <= max_b4 ? 4 : 1);
+// k_linesearch<spec, 0, waves, world_wrench> (waves 1, 2 or 4; 64 threads per wave)
+template <bool SPEC, bool FW>
+auto ls_kernel_w(int waves) {
+  return waves == 4 ? k_linesearch<SPEC, 0, 4, FW> : waves == 2 ? k_linesearch<SPEC, 0, 2, FW> : k_linesearch<SPEC, 0, 1, FW>;
+}
+auto ls_kernel(bool spec, bool world_wrench, int waves) {
+  if (spec) return world_wrench ? ls_kernel_w<true, true>(waves) : ls_kernel_w<true, false>(waves);
+  return world_wrench ? ls_kernel_w<false, true>(waves) : ls_kernel_w<false, false>(waves);
 }
 
 // base_from_lin: lin/cost of W hold the linearisation of this xu (the SQP loop), so the base
@@ -468,38 +398,29 @@ int launch_linesearch(i7m_handle* h, hipStream_t s, const Bufs& W, const SolvePa
                       double* xu_out, const double* sol, const double* goals, int* active, ProblemStats* st,
                       double* alpha_out, int iter, int mode, bool base_from_lin) {
   if (P.B == 0) return I7M_OK;
-  // small batches leave most SIMDs idle: spend them on evaluating every candidate in one round
-  const int nw = waves_for(h, P.B);
+  const int nw = ls_waves(h->tune, P.B);
   const size_t lds = ls_lds_bytes(P.T, nw);
   const double* ln = base_from_lin ? W.lin : nullptr;
   const double* cs = base_from_lin ? W.cost : nullptr;
   const bool fw = W.fext && h->fext_frame == I7M_WRENCH_WORLD;
-  if (h->ls_tail > 0 && nw == 1 && mode == 0 && base_from_lin) {
+  if (h->tune.ls_tail > 0 && nw == 1 && mode == 0 && base_from_lin) {
     // split search: r rounds of one wave per problem, then two waves per problem
     // for the problems that have not accepted a candidate
     const int R = P.N >= 64 ? 1 : 64 / P.N;
-    const int c_split = 1 + R * h->ls_tail;
+    const int c_split = 1 + R * h->tune.ls_tail;
     const long b0 = W.lin - h->d_lin;  // this range's first problem (bufs_at offsets lin by b0 (N-1) stride)
     const long pb = b0 / ((long)(P.N - 1) * LIN_STRIDE);
     const LsSplit first{0, c_split, h->d_lsbase + pb, h->d_lspend + pb};
     const LsSplit second{c_split, 1 + NALPHA, h->d_lsbase + pb, h->d_lspend + pb};
     int rc = timed(h, s, I7M_K_LINESEARCH, [&](hipEvent_t ea, hipEvent_t eb) {
-      auto go = [&](auto kern) {
-        hipExtLaunchKernelGGL(kern, dim3(P.B), dim3(64), lds, s, ea, eb, 0, h->d_model, P, xu, xu_out, sol, goals, W.fext,
-                              active, st, alpha_out, iter, mode, W.lin, W.cost, first);
-      };
-      if (h->spec) fw ? go(k_linesearch<true, 0, 1, true>) : go(k_linesearch<true, 0, 1>);
-      else fw ? go(k_linesearch<false, 0, 1, true>) : go(k_linesearch<false, 0, 1>);
+      hipExtLaunchKernelGGL(ls_kernel(h->spec, fw, 1), dim3(P.B), dim3(64), lds, s, ea, eb, 0, h->d_model, P, xu, xu_out, sol,
+                            goals, W.fext, active, st, alpha_out, iter, mode, W.lin, W.cost, first);
     });
     if (rc) return rc;
     const size_t lds2 = ls_lds_bytes(P.T, 2);
     return timed(h, s, I7M_K_LINESEARCH_TAIL, [&](hipEvent_t ea, hipEvent_t eb) {
-      auto go = [&](auto kern) {
-        hipExtLaunchKernelGGL(kern, dim3(P.B), dim3(128), lds2, s, ea, eb, 0, h->d_model, P, xu, xu_out, sol, goals, W.fext,
-                              active, st, alpha_out, iter, mode, W.lin, W.cost, second);
-      };
-      if (h->spec) fw ? go(k_linesearch<true, 0, 2, true>) : go(k_linesearch<true, 0, 2>);
-      else fw ? go(k_linesearch<false, 0, 2, true>) : go(k_linesearch<false, 0, 2>);
+      hipExtLaunchKernelGGL(ls_kernel(h->spec, fw, 2), dim3(P.B), dim3(128), lds2, s, ea, eb, 0, h->d_model, P, xu, xu_out,
+                            sol, goals, W.fext, active, st, alpha_out, iter, mode, W.lin, W.cost, second);
     });
   }
   return timed(h, s, I7M_K_LINESEARCH, [&](hipEvent_t ea, hipEvent_t eb) {
@@ -513,16 +434,7 @@ int launch_linesearch(i7m_handle* h, hipStream_t s, const Bufs& W, const SolvePa
       return;
     }
 #endif
-    if (nw == 4) {
-      if (h->spec) fw ? go(k_linesearch<true, 0, 4, true>, 256) : go(k_linesearch<true, 0, 4>, 256);
-      else fw ? go(k_linesearch<false, 0, 4, true>, 256) : go(k_linesearch<false, 0, 4>, 256);
-    } else if (nw == 2) {  // A/B only (I7M_LS_WAVES=2)
-      if (h->spec) fw ? go(k_linesearch<true, 0, 2, true>, 128) : go(k_linesearch<true, 0, 2>, 128);
-      else fw ? go(k_linesearch<false, 0, 2, true>, 128) : go(k_linesearch<false, 0, 2>, 128);
-    } else {
-      if (h->spec) fw ? go(k_linesearch<true, 0, 1, true>, 64) : go(k_linesearch<true, 0, 1>, 64);
-      else fw ? go(k_linesearch<false, 0, 1, true>, 64) : go(k_linesearch<false, 0, 1>, 64);
-    }
+    go(ls_kernel(h->spec, fw, nw), 64 * nw);  // (two waves: A/B only, I7M_LS_WAVES=2)
   });
 }
 
@@ -537,11 +449,26 @@ BoxParams box_params(const i7m_handle* h) {
   return BP;
 }
 
+// The staggered ranges' mark (Tuning::admm_stagger): the first range's (or chunk's) first run_sqp
+// records `ev` on its stream at point `at` — 1: after its first QP's scaling and factor, 2: after
+// its first QP — and the second range waits for it iff it was recorded.
+struct StaggerMark {
+  hipEvent_t ev;
+  int at;
+  bool recorded;
+};
+int record_mark(StaggerMark* m, int at, hipStream_t s) {
+  if (!m || m->recorded || m->at != at) return I7M_OK;
+  HIPCHK(hipEventRecord(m->ev, s));
+  m->recorded = true;
+  return I7M_OK;
+}
+
 // The QP of one SQP iteration: the exact equality-constrained solve (k_riccati_mfma), and in
 // box mode the interior-point iteration started from it (i7m_box.h; oracle/box_ipm.py).
 // Returns where the minimiser is: `sol`, or W.bx in box mode.
 int solve_qp(i7m_handle* h, hipStream_t s, const Bufs& W, const SolveParams& P, const double* xu, const double* xs,
-             const int* active, double* sol, const double** out, int sqp_iter = 0) {
+             const int* active, double* sol, const double** out, int sqp_iter = 0, StaggerMark* mark = nullptr) {
   int rc;
   if (h->cfg.qp_mode == I7M_QP_ADMM) {
     // OSQP's iteration from the problems' carried state (i7m_admm.h; oracle/osqp_admm.py)
@@ -561,67 +488,46 @@ int solve_qp(i7m_handle* h, hipStream_t s, const Bufs& W, const SolveParams& P, 
 #ifdef I7M_DIAG
     a.ablate = h->ablate;
 #endif
-    // I7M_ADMM_CHUNK = c > 0: the batch as consecutive launches of c problems, so one launch's
-    // factors (the blocks every OSQP iteration re-reads) can stay in the 256 MB MALL
-    const int chunk = h->admm_chunk > 0 ? std::min(h->admm_chunk, P.B) : P.B;
-    for (int lo = 0; lo < P.B; lo += chunk) {
-      a.b0 = lo;
-      const int n = std::min(chunk, P.B - lo);
-      int rc2 = timed(h, s, I7M_K_ADMM_PREP, [&](hipEvent_t ea, hipEvent_t eb) {
-        // scaling, then the factor (one event pair around both)
-        // the max-ILP-scheduled copies (i7m_admm_prep_tu.hip) or this unit's (default scheduler)
-        const bool ilp = h->admm_prep_ilp > 0 || (h->admm_prep_ilp < 0 && n <= h->admm_prep_ilp_max);
-        if (ilp)
-          (void)i7m_launch_admm_prep(P.N <= 32 ? 0 : 1, n, s, ea, nullptr, &a);
-        else if (P.N <= 32)
-          hipExtLaunchKernelGGL(k_admm_scale<9>, dim3(n), dim3(64), 0, s, ea, nullptr, 0, a);
-        else
-          hipExtLaunchKernelGGL(k_admm_scale<18>, dim3(n), dim3(64), 0, s, ea, nullptr, 0, a);
-        if (h->mark_ev && h->admm_stagger == 4) {  // (A/B: the mark between scaling and factor)
-          (void)hipEventRecord(h->mark_ev, s);
-          h->mark_ev = nullptr;
-        }
-        if (ilp)
-          (void)i7m_launch_admm_prep(2, n, s, nullptr, eb, &a);
-        else
-          hipExtLaunchKernelGGL(k_admm_factor, dim3(n), dim3(64), 0, s, nullptr, eb, 0, a);
-      });
-      if (rc2) return rc2;
-      if (h->mark_ev && h->admm_stagger == 1) {
-        HIPCHK(hipEventRecord(h->mark_ev, s));
-        h->mark_ev = nullptr;
+    a.b0 = 0;
+    const int n = P.B;
+    hipError_t e = hipSuccess;
+    rc = timed(h, s, I7M_K_ADMM_PREP, [&](hipEvent_t ea, hipEvent_t eb) {
+      // scaling, then the factor (one event pair around both)
+      // the max-ILP-scheduled copies (i7m_admm_prep_tu.hip) or this unit's (default scheduler)
+      if (admm_prep_ilp(h->tune, n)) {
+        e = i7m_launch_admm_prep(P.N <= 32 ? 0 : 1, n, s, ea, nullptr, &a);
+        if (e == hipSuccess) e = i7m_launch_admm_prep(2, n, s, nullptr, eb, &a);
+        return;
       }
-      rc2 = timed(h, s, I7M_K_ADMM, [&](hipEvent_t ea, hipEvent_t eb) {
-        // four problems per wave: the launch covers [lo, lo + n) (a.b0 = lo), rows past it idle
-        SolveParams P4 = a.P;
-        P4.B = lo + n;
-        AdmmArgs a4 = a;
-        a4.P = P4;
-        const dim3 g((n + 3) / 4);
-        const bool res_fits = !a.A.adapt_interval && a.P.N <= ARES_N;
-        if (a.A.adapt_interval)
-          hipExtLaunchKernelGGL(k_admm_iter<true>, g, dim3(64), 0, s, ea, eb, 0, a4);
-        else if (res_fits && (h->admm_res > 0 || (h->admm_res < 0 && n <= h->admm_res_max)))
-          hipExtLaunchKernelGGL(k_admm_iter_res, dim3(n), dim3(64), 0, s, ea, eb, 0, a4);
-        else if (h->admm_iter2 > 0 || (h->admm_iter2 < 0 && n <= 512))  // two problems per wave
-          hipExtLaunchKernelGGL(k_admm_iter2, dim3((n + 1) / 2), dim3(64), 0, s, ea, eb, 0, a4);
-        else
-          hipExtLaunchKernelGGL(k_admm_iter<false>, g, dim3(64), h->admm_iter_dyn_lds, s, ea, eb, 0, a4);
-      });
-      if (rc2) return rc2;
-    }
-    if (h->mark_ev && h->admm_stagger == 2) {
-      HIPCHK(hipEventRecord(h->mark_ev, s));
-      h->mark_ev = nullptr;
-    }
-    return I7M_OK;
+      if (P.N <= 32)
+        hipExtLaunchKernelGGL(k_admm_scale<9>, dim3(n), dim3(64), 0, s, ea, nullptr, 0, a);
+      else
+        hipExtLaunchKernelGGL(k_admm_scale<18>, dim3(n), dim3(64), 0, s, ea, nullptr, 0, a);
+      hipExtLaunchKernelGGL(k_admm_factor, dim3(n), dim3(64), 0, s, nullptr, eb, 0, a);
+    });
+    if (rc) return rc;
+    if (e != hipSuccess) return fail(I7M_EHIP, std::string("k_admm_scale / k_admm_factor launch: ") + hipGetErrorString(e));
+    if ((rc = record_mark(mark, 1, s))) return rc;
+    rc = timed(h, s, I7M_K_ADMM, [&](hipEvent_t ea, hipEvent_t eb) {
+      const dim3 g((n + 3) / 4);  // four problems per wave, rows past the batch idle
+      switch (admm_iter_kernel(h->tune, P.N, a.A.adapt_interval != 0, n)) {
+        case AdmmIter::adapt: hipExtLaunchKernelGGL(k_admm_iter<true>, g, dim3(64), 0, s, ea, eb, 0, a); break;
+        case AdmmIter::res: hipExtLaunchKernelGGL(k_admm_iter_res, dim3(n), dim3(64), 0, s, ea, eb, 0, a); break;
+        case AdmmIter::iter2:  // two problems per wave
+          hipExtLaunchKernelGGL(k_admm_iter2, dim3((n + 1) / 2), dim3(64), 0, s, ea, eb, 0, a);
+          break;
+        case AdmmIter::iter4: hipExtLaunchKernelGGL(k_admm_iter<false>, g, dim3(64), 0, s, ea, eb, 0, a); break;
+      }
+    });
+    if (rc) return rc;
+    return record_mark(mark, 2, s);
   }
   if ((rc = launch_riccati(h, s, W, P, xu, xs, active, sol))) return rc;
   *out = sol;
   if (h->cfg.qp_mode != I7M_QP_BOX || P.B == 0) return I7M_OK;
   const BoxParams BP = box_params(h);
   const dim3 g(P.B), blk(64);
-  if (h->ipm_mode != 2) {
+  if (h->tune.ipm_mode != 2) {
 #ifdef I7M_DIAG
     const IpmFusedArgs fa{h->d_model, P, BP, xu, xs, W.lin, W.cost, W.qpd, active, W.kbuf, sol, sol,
                           W.bx, W.bzl, W.bzu, W.bsig, W.bh, W.bdxa, W.bst, W.bact, W.bhinv, W.bdh, h->ablate};
@@ -630,7 +536,7 @@ int solve_qp(i7m_handle* h, hipStream_t s, const Bufs& W, const SolveParams& P, 
                           W.bx, W.bzl, W.bzu, W.bsig, W.bh, W.bdxa, W.bst, W.bact, W.bhinv, W.bdh};
 #endif
     rc = timed(h, s, I7M_K_IPM_FUSED, [&](hipEvent_t ea, hipEvent_t eb) {
-      if (h->ipm_mode == 0)
+      if (h->tune.ipm_mode == 0)
         hipExtLaunchKernelGGL(k_ipm_fused<true>, g, blk, 0, s, ea, eb, 0, fa);
       else
         hipExtLaunchKernelGGL(k_ipm_fused<false>, g, blk, 0, s, ea, eb, 0, fa);
@@ -666,21 +572,11 @@ int solve_qp(i7m_handle* h, hipStream_t s, const Bufs& W, const SolveParams& P, 
   return I7M_OK;
 }
 
-// Does this solve run as one k_sqp_fused launch?  (Direct QP only; the box mode's interior point
-// has its own fused kernel between the Riccati and the line search.)  AUTO is the split pipeline
-// at every batch size: the fused one measured 1.1-2.4x slower from B = 1 to 4096.
-bool use_fused(const i7m_handle* h, int B) {
-  (void)B;
-  if (h->cfg.qp_mode != I7M_QP_DIRECT) return false;
-  return h->pipeline == I7M_PIPE_FUSED || h->pipeline == I7M_PIPE_FUSED_ITER;
-}
-
-
 int launch_fused(i7m_handle* h, hipStream_t s, const Bufs& W, const SolveParams& P, const double* xu_in, double* xu_out,
                  const double* xs, const double* goals, ProblemStats* st, long b0) {
-  const int nw = waves_for(h, P.B, FUSED_W4_MAX_B);
+  const int nw = fused_waves(h->tune, P.B);
   // I7M_PIPE_FUSED_ITER: one launch per SQP iteration, else one per solve
-  const int launches = h->pipeline == I7M_PIPE_FUSED_ITER ? h->cfg.max_sqp_iters : 1;
+  const int launches = h->tune.pipeline == I7M_PIPE_FUSED_ITER ? h->cfg.max_sqp_iters : 1;
   for (int i = 0; i < launches; ++i) {
     hipError_t e = hipSuccess;
     const int rc = timed(h, s, I7M_K_SQP_FUSED, [&](hipEvent_t ea, hipEvent_t eb) {
@@ -701,14 +597,15 @@ int launch_fused(i7m_handle* h, hipStream_t s, const Bufs& W, const SolveParams&
 // stream s (h->stream unless the host-to-host path splits the batch into chunks).
 // (Splitting a device-resident batch into ranges on several streams, so that waves of different
 // kernels share a SIMD, was measured at 2-4 ranges and gave nothing: DESIGN.md §7.)
+// mark: the staggered ranges' mark, recorded in this solve's first QP (ADMM mode; StaggerMark).
 int run_sqp(i7m_handle* h, int B, const double* d_xu_in, double* d_xu, const double* d_xs, const double* d_goals,
-            int goal_stride, ProblemStats* d_st, long b0 = 0, hipStream_t s = nullptr) {
+            int goal_stride, ProblemStats* d_st, long b0 = 0, hipStream_t s = nullptr, StaggerMark* mark = nullptr) {
   const Bufs W = bufs_at(h, b0);
   const SolveParams P = params_of(h, B, goal_stride);
   if (!s) s = h->stream;
   int* act = h->d_active + b0;
   double* qbuf = h->d_sol + b0 * P.T;
-  if (use_fused(h, B)) return launch_fused(h, s, W, P, d_xu_in, d_xu, d_xs, d_goals, d_st, b0);
+  if (use_fused(h->tune, h->cfg.qp_mode)) return launch_fused(h, s, W, P, d_xu_in, d_xu, d_xs, d_goals, d_st, b0);
   if (h->cfg.qp_mode == I7M_QP_ADMM && B > 0) {
     // this solve's OSQP records start at -1 ("no QP"): a problem that stops after SQP iteration
     // 0 must not report an earlier call's counts for the iterations it did not run
@@ -723,19 +620,8 @@ int run_sqp(i7m_handle* h, int B, const double* d_xu_in, double* d_xu, const dou
     else
       rc = launch_linearize(h, s, W, P, xin, d_goals, act);
     if (rc) return rc;
-    // the staggered ranges' mark outside ADMM mode (which marks inside its QP): after the first
-    // linearisation (admm_stagger 1) or the first QP (2)
-    const bool mark_here = h->mark_ev && h->cfg.qp_mode != I7M_QP_ADMM;
-    if (h->mark_ev && (h->admm_stagger == 3 || (mark_here && h->admm_stagger == 1))) {
-      HIPCHK(hipEventRecord(h->mark_ev, s));
-      h->mark_ev = nullptr;
-    }
     const double* qsol = nullptr;
-    if ((rc = solve_qp(h, s, W, P, xin, d_xs, act, qbuf, &qsol, it))) return rc;
-    if (mark_here && h->mark_ev && h->admm_stagger == 2) {
-      HIPCHK(hipEventRecord(h->mark_ev, s));
-      h->mark_ev = nullptr;
-    }
+    if ((rc = solve_qp(h, s, W, P, xin, d_xs, act, qbuf, &qsol, it, mark))) return rc;
     // mode 2: the ADMM mode's QP solver carries state, so an alpha = 0 iteration is re-solved
     if ((rc = launch_linesearch(h, s, W, P, xin, d_xu, qsol, d_goals, act, d_st, nullptr, it,
                                 h->cfg.qp_mode == I7M_QP_ADMM ? 2 : 0, h->ablate != 6)))
@@ -755,7 +641,7 @@ void drop_graphs(i7m_handle* h) {
 // sequence once.  Timing runs (events) and multi-range runs go direct.
 int run_sqp_graphed(i7m_handle* h, int B, const double* d_xu_in, double* d_xu, const double* d_xs, const double* d_goals,
                     int goal_stride, ProblemStats* d_st) {
-  if (!h->use_graph || h->timing)
+  if (!h->tune.use_graph || h->timing)
     return run_sqp(h, B, d_xu_in, d_xu, d_xs, d_goals, goal_stride, d_st);
   const int hf = h->has_fext ? 1 : 0;
   i7m_handle::GraphEntry* hit = nullptr;
@@ -792,24 +678,6 @@ int run_sqp_graphed(i7m_handle* h, int B, const double* d_xu_in, double* d_xu, c
   return I7M_OK;
 }
 
-// chunks of a host-to-host solve of B problems: the handle's setting, else automatic — three
-// (tapered) from 3 072 problems, two from 2 048, one piece below (config 3: 1.42 -> 1.21 ms;
-// at B = 1 024 one piece is fastest; DESIGN.md §5 has the A/B)
-// Does a batch of B run as staggered ranges (i7m_handle::admm_stagger)?
-bool stagger_applies(const i7m_handle* h, int B) {
-  return ((h->stagger_modes >> h->cfg.qp_mode) & 1) && h->admm_stagger > 0 && h->admm_ranges > 1 &&
-         B >= h->admm_stagger_min_b && h->dev_ranges <= 1;
-}
-
-
-int h2h_chunks_for(const i7m_handle* h, int B) {
-  if (h->h2h_chunks > 0) return h->h2h_chunks;
-  // ADMM mode where the device solve staggers: two chunks, the second's solve behind the first's
-  // mark (solve_h2h_pipelined_body), i.e. the staggered halves with the copies overlapped
-  if (h->cfg.qp_mode == I7M_QP_ADMM && stagger_applies(h, B)) return 2;
-  return B >= 3072 ? 3 : (B >= 2048 ? 2 : 1);
-}
-
 int copy_in(i7m_handle* h, double* dst, const double* src, size_t n, hipStream_t s = nullptr) {
   if (n) HIPCHK(hipMemcpyAsync(dst, src, n * sizeof(double), hipMemcpyHostToDevice, s ? s : h->stream));
   return I7M_OK;
@@ -833,7 +701,7 @@ int solve_h2h_chunked_body(i7m_handle* h, int B, const double* xu_in, const doub
   HIPCHK(hipEventRecord(h->ev_order, h->stream));
   for (int c = 0; c < 2; ++c) HIPCHK(hipStreamWaitEvent(h->cs[c], h->ev_order, 0));
   for (int i = 0; i < nch; ++i) {
-    const long lo = (long)B * i / nch, hi = (long)B * (i + 1) / nch;
+    const long lo = chunk_lo(B, nch, i, false), hi = chunk_lo(B, nch, i + 1, false);
     const int n = (int)(hi - lo);
     if (n == 0) continue;
     hipStream_t s = h->cs[i & 1];
@@ -879,19 +747,12 @@ int solve_h2h_pipelined_body(i7m_handle* h, int B, const double* xu_in, const do
     h->ev_cmp.push_back(b);
   }
   int rc;
-  if (h->h2h_pipe >= 2 && !h->cs2) HIPCHK(hipStreamCreateWithFlags(&h->cs2, hipStreamNonBlocking));
+  if (h->tune.h2h_pipe >= 2 && !h->cs2) HIPCHK(hipStreamCreateWithFlags(&h->cs2, hipStreamNonBlocking));
   HIPCHK(hipEventRecord(h->ev_order, h->stream));
   for (int c = 0; c < 2; ++c) HIPCHK(hipStreamWaitEvent(h->cs[c], h->ev_order, 0));
-  if (h->h2h_pipe >= 2) HIPCHK(hipStreamWaitEvent(h->cs2, h->ev_order, 0));
-  auto sstream = [&](int i) { return (h->h2h_pipe >= 2 && (i & 1)) ? h->cs2 : h->stream; };
-  // taper (default; I7M_H2H_TAPER=0 for equal chunks): the first and the last chunk half the size
-  // of the others, so the copy-in before the first solve and the copy-out after the last are short
-  auto lo_of = [&](int i) -> long {
-    if (!h->h2h_taper || nch < 3) return (long)B * i / nch;
-    if (i == 0) return 0;
-    if (i == nch) return B;
-    return (long)((double)B * (2 * i - 1) / (2.0 * (nch - 1)));
-  };
+  if (h->tune.h2h_pipe >= 2) HIPCHK(hipStreamWaitEvent(h->cs2, h->ev_order, 0));
+  auto sstream = [&](int i) { return (h->tune.h2h_pipe >= 2 && (i & 1)) ? h->cs2 : h->stream; };
+  auto lo_of = [&](int i) { return chunk_lo(B, nch, i, h->tune.h2h_taper != 0); };
   // (each stage keeps its status in a local: with h2h_pipe 3 out() runs on another thread)
   auto in = [&](int i) -> int {
     const long lo = lo_of(i), n = lo_of(i + 1) - lo;
@@ -905,22 +766,17 @@ int solve_h2h_pipelined_body(i7m_handle* h, int B, const double* xu_in, const do
   };
   // ADMM mode where the device solve staggers, in two chunks: the second chunk's solve also waits
   // for the first's mark (its first scaling + factor), as the staggered halves of i7m_solve_device
-  const bool stag = nch == 2 && h->cfg.qp_mode == I7M_QP_ADMM && stagger_applies(h, B);
-  if (stag && !h->ev_rmark[0]) HIPCHK(hipEventCreateWithFlags(&h->ev_rmark[0], hipEventDisableTiming));
-  bool marked0 = false;
+  const bool stag = nch == 2 && stagger_applies(h->tune, h->cfg.qp_mode, B);
+  StaggerMark mark{h->ev_rmark, h->tune.admm_stagger, false};
   auto solve = [&](int i) -> int {
     const long lo = lo_of(i), n = lo_of(i + 1) - lo;
     const hipStream_t ss = sstream(i);
     HIPCHK(hipStreamWaitEvent(ss, h->ev_in[i], 0));
-    if (stag && i == 1 && marked0) HIPCHK(hipStreamWaitEvent(ss, h->ev_rmark[0], 0));
+    if (i == 1 && mark.recorded) HIPCHK(hipStreamWaitEvent(ss, mark.ev, 0));
     double* dxu = h->d_xu + lo * T;
-    int r;
-    h->mark_ev = stag && i == 0 ? h->ev_rmark[0] : nullptr;
-    r = n > 0 ? run_sqp(h, (int)n, dxu, dxu, h->d_xs + lo * 12, h->d_goal + lo * N * goal_stride, goal_stride,
-                        h->d_stats + lo, lo, ss)
-              : I7M_OK;
-    if (stag && i == 0) marked0 = !h->mark_ev;
-    h->mark_ev = nullptr;
+    const int r = n > 0 ? run_sqp(h, (int)n, dxu, dxu, h->d_xs + lo * 12, h->d_goal + lo * N * goal_stride, goal_stride,
+                                  h->d_stats + lo, lo, ss, stag && i == 0 ? &mark : nullptr)
+                        : I7M_OK;
     if (r) return r;
     HIPCHK(hipEventRecord(h->ev_cmp[i], ss));
     return I7M_OK;
@@ -935,7 +791,7 @@ int solve_h2h_pipelined_body(i7m_handle* h, int B, const double* xu_in, const do
                             h->cs[1]));
     return I7M_OK;
   };
-  if (h->h2h_pipe == 3) {
+  if (h->tune.h2h_pipe == 3) {
     // copies out on a second host thread: a pageable copy blocks the thread that issues it, so
     // with one thread every copy-out sat between two copy-ins and the link ran one direction at a
     // time; here the calling thread issues in(0) solve(0) in(1) solve(1) ... back to back while the
@@ -994,8 +850,6 @@ int drain_after_error(i7m_handle* h, int rc) {
   for (int c = 0; c < 2; ++c)
     if (h->cs[c]) (void)hipStreamSynchronize(h->cs[c]);
   if (h->cs2) (void)hipStreamSynchronize(h->cs2);
-  for (int r = 2; r < i7m_handle::kMaxRanges; ++r)  // the staggered ranges' own streams
-    if (h->rs[r]) (void)hipStreamSynchronize(h->rs[r]);
   (void)hipStreamSynchronize(h->stream);
   g_err = msg;
   return rc;
@@ -1006,7 +860,7 @@ int solve_h2h_pipelined(i7m_handle* h, int B, const double* xu_in, const double*
 }
 int solve_h2h_chunked(i7m_handle* h, int B, const double* xu_in, const double* xcur, const double* goals, int goal_stride,
                       double* xu_out, i7m_problem_stats* stats, int nch) {
-  if (h->h2h_pipe) return solve_h2h_pipelined(h, B, xu_in, xcur, goals, goal_stride, xu_out, stats, nch);
+  if (h->tune.h2h_pipe) return solve_h2h_pipelined(h, B, xu_in, xcur, goals, goal_stride, xu_out, stats, nch);
   return drain_after_error(h, solve_h2h_chunked_body(h, B, xu_in, xcur, goals, goal_stride, xu_out, stats, nch));
 }
 
@@ -1139,49 +993,16 @@ int i7m_create(const i7m_config* cfg, i7m_handle** out) {
     return bail(fail(I7M_EINVAL, "I7M_ABLATE is set, but this is the release library: the ablation "
                                  "timing kernels exist only in the -DI7M_DIAG build (tools/)"));
 #endif
-  if (const char* e = std::getenv("I7M_IPM"))
-    h->ipm_mode = std::strcmp(e, "split") == 0 ? 2 : (std::strcmp(e, "delta") == 0 ? 0 : 1);
-  if (const char* e = std::getenv("I7M_LS_TAIL")) h->ls_tail = std::min(std::max(std::atoi(e), 0), 3);
-  if (const char* e = std::getenv("I7M_LS_WAVES")) h->ls_waves = std::atoi(e) == 4 ? 4 : (std::atoi(e) == 2 ? 2 : 1);
-  if (const char* e = std::getenv("I7M_GRAPH")) h->use_graph = std::atoi(e) != 0;
-  if (const char* e = std::getenv("I7M_RIC_W2")) h->ric_w2 = std::atoi(e) != 0;
-  if (const char* e = std::getenv("I7M_RIC_BC")) {
-    const int v = std::atoi(e) & 7;
-    h->ric_bc = (v == 4 || v == 5) ? (v & 3) : v;  // instantiated: 0 1 2 3 6 7
-  }
-  h->h2h_chunks = cfg->h2h_chunks;
-  if (const char* e = std::getenv("I7M_H2H_CHUNKS")) h->h2h_chunks = std::atoi(e);
-  if (const char* e = std::getenv("I7M_H2H_PIPE")) h->h2h_pipe = std::min(std::max(std::atoi(e), 0), 3);
-  if (const char* e = std::getenv("I7M_H2H_TAPER")) h->h2h_taper = std::atoi(e) != 0;
-  if (const char* e = std::getenv("I7M_ADMM_CHUNK")) h->admm_chunk = std::max(std::atoi(e), 0);
-  if (const char* e = std::getenv("I7M_DEV_RANGES")) h->dev_ranges = std::min(std::max(std::atoi(e), 0), 64);
-  if (const char* e = std::getenv("I7M_ADMM_STAGGER")) h->admm_stagger = std::min(std::max(std::atoi(e), 0), 4);
-  if (const char* e = std::getenv("I7M_ADMM_STAGGER_MIN_B")) h->admm_stagger_min_b = std::max(std::atoi(e), 2);
-  if (const char* e = std::getenv("I7M_ADMM_SPLIT")) h->admm_split = std::min(std::max(std::atoi(e), 100), 900);
-  if (const char* e = std::getenv("I7M_STAGGER_MODES")) h->stagger_modes = std::atoi(e);
-  if (const char* e = std::getenv("I7M_ADMM_RANGES"))
-    h->admm_ranges = std::min(std::max(std::atoi(e), 1), (int)i7m_handle::kMaxRanges);
-  if (const char* e = std::getenv("I7M_ADMM_CHAINS")) h->admm_chains = std::min(std::max(std::atoi(e), 1), 2);
-  if (const char* e = std::getenv("I7M_ADMM_ITER2")) h->admm_iter2 = std::min(std::max(std::atoi(e), -1), 1);
-  if (const char* e = std::getenv("I7M_ADMM_RES")) h->admm_res = std::min(std::max(std::atoi(e), -1), 1);
-  if (const char* e = std::getenv("I7M_ADMM_RES_MAX")) h->admm_res_max = std::max(std::atoi(e), 0);
-  if (const char* e = std::getenv("I7M_ADMM_PREP_ILP")) h->admm_prep_ilp = std::min(std::max(std::atoi(e), -1), 1);
-  if (const char* e = std::getenv("I7M_ADMM_PREP_ILP_MAX")) h->admm_prep_ilp_max = std::max(std::atoi(e), 0);
-  if (const char* e = std::getenv("I7M_ADMM_ITER_DYN_LDS")) h->admm_iter_dyn_lds = std::min(std::max(std::atoi(e), 0), 65536);
-  if (h->h2h_chunks < 0 || h->h2h_chunks > 64) return bail(fail(I7M_EINVAL, "h2h_chunks must be in [0, 64]"));
+  std::string tune_err;
+  if (!tuning_from_env(*cfg, &h->tune, &tune_err)) return bail(fail(I7M_EINVAL, tune_err));
   if (hipStreamCreateWithFlags(&h->cs[0], hipStreamNonBlocking) != hipSuccess ||
       hipStreamCreateWithFlags(&h->cs[1], hipStreamNonBlocking) != hipSuccess ||
       hipEventCreateWithFlags(&h->ev_order, hipEventDisableTiming) != hipSuccess ||
       hipEventCreateWithFlags(&h->ev_done[0], hipEventDisableTiming) != hipSuccess ||
-      hipEventCreateWithFlags(&h->ev_done[1], hipEventDisableTiming) != hipSuccess)
+      hipEventCreateWithFlags(&h->ev_done[1], hipEventDisableTiming) != hipSuccess ||
+      hipEventCreateWithFlags(&h->ev_rmark, hipEventDisableTiming) != hipSuccess)
     return bail(fail(I7M_EHIP, "chunk stream / event creation failed"));
-  h->pipeline = cfg->pipeline;
-  if (const char* e = std::getenv("I7M_PIPE"))
-    h->pipeline = std::strcmp(e, "fused") == 0 ? I7M_PIPE_FUSED
-                   : std::strcmp(e, "fused_iter") == 0 ? I7M_PIPE_FUSED_ITER
-                   : std::strcmp(e, "split") == 0 ? I7M_PIPE_SPLIT
-                   : h->pipeline;
-  if (h->pipeline == I7M_PIPE_FUSED || h->pipeline == I7M_PIPE_FUSED_ITER) {
+  if (h->tune.pipeline == I7M_PIPE_FUSED || h->tune.pipeline == I7M_PIPE_FUSED_ITER) {
     const hipError_t ef = i7m_prepare_sqp_fused(h->dev, cfg->N);
     if (ef != hipSuccess) return bail(fail(I7M_EHIP, std::string("k_sqp_fused LDS limit: ") + hipGetErrorString(ef)));
   }
@@ -1218,8 +1039,7 @@ int i7m_create(const i7m_config* cfg, i7m_handle** out) {
   if (!ok) return bail(fail(I7M_ENOMEM, "hipMalloc failed for max_batch=" + std::to_string(cfg->max_batch)));
   DevModel dm = make_dev_model(cfg->model);
   // the Indy7-specialised kernels are used only for a model bit-identical to the baked one
-  h->spec = std::memcmp(&dm, &kIndy7Model, sizeof(DevModel)) == 0;
-  if (const char* e = std::getenv("I7M_GENERIC")) h->spec = h->spec && std::atoi(e) == 0;
+  h->spec = std::memcmp(&dm, &kIndy7Model, sizeof(DevModel)) == 0 && !h->tune.generic;
   if (hipMemcpy(h->d_model, &dm, sizeof(dm), hipMemcpyHostToDevice) != hipSuccess)
     return bail(fail(I7M_EHIP, "model upload failed"));
   *out = h;
@@ -1256,14 +1076,7 @@ void i7m_destroy(i7m_handle* h) {
     if (h->ev_done[c]) (void)hipEventDestroy(h->ev_done[c]);
   }
   if (h->ev_order) (void)hipEventDestroy(h->ev_order);
-  for (int r = 0; r < i7m_handle::kMaxRanges; ++r) {
-    if (h->rs[r]) {
-      (void)hipStreamSynchronize(h->rs[r]);
-      (void)hipStreamDestroy(h->rs[r]);
-    }
-    if (h->ev_rmark[r]) (void)hipEventDestroy(h->ev_rmark[r]);
-    if (h->ev_rdone[r]) (void)hipEventDestroy(h->ev_rdone[r]);
-  }
+  if (h->ev_rmark) (void)hipEventDestroy(h->ev_rmark);
   if (h->own) (void)hipStreamDestroy(h->own);
   delete h;
 }
@@ -1402,60 +1215,36 @@ int i7m_synchronize(i7m_handle* h) {
 }
 
 extern "C++" {  // (C++ helpers inside the C-ABI block)
-// The batch as h->admm_ranges contiguous ranges, each on a stream of its own and started when
-// the range before it has passed its mark (the first run_sqp of its `body` records it; see
-// i7m_handle::admm_stagger), every range forked from and joined back into h->stream.
-// body(lo, n, stream) enqueues the work of problems [lo, lo + n).  Results are the one-range
-// run's: the problems are independent.
+// The batch as two contiguous ranges (stagger_cut) on cs[0] and cs[1], the second started when the
+// first has passed its mark (the first run_sqp of its `body` records it; StaggerMark), both
+// forked from and joined back into h->stream.  body(lo, n, stream, mark) enqueues the work of
+// problems [lo, lo + n).  Results are the one-range run's: the problems are independent.
 template <class Body>
 static int run_staggered(i7m_handle* h, int B, Body&& body) {
-  const int R = h->admm_ranges;
-  hipStream_t ss[i7m_handle::kMaxRanges];
-  for (int r = 0; r < R; ++r) {
-    if (r < 2) {
-      ss[r] = h->cs[r];
-    } else {
-      if (!h->rs[r]) HIPCHK(hipStreamCreateWithFlags(&h->rs[r], hipStreamNonBlocking));
-      ss[r] = h->rs[r];
-    }
-    if (!h->ev_rmark[r]) HIPCHK(hipEventCreateWithFlags(&h->ev_rmark[r], hipEventDisableTiming));
-    if (!h->ev_rdone[r]) HIPCHK(hipEventCreateWithFlags(&h->ev_rdone[r], hipEventDisableTiming));
-  }
-  // range boundaries, clamped to [0, B] (the rounded split of a small B or an extreme
-  // I7M_ADMM_SPLIT must not run past the batch); an empty range is skipped
-  auto cut = [&](int q) {
-    const long c = R == 2 && q == 1 ? ((long)B * h->admm_split / 1000 + 3) / 4 * 4 : (long)B * q / R;
-    return std::min<long>(std::max<long>(c, 0), B);
-  };
+  const long cuts[3] = {0, stagger_cut(B), B};
+  StaggerMark mark{h->ev_rmark, h->tune.admm_stagger, false};
   HIPCHK(hipEventRecord(h->ev_order, h->stream));
-  // range r starts behind range r - C's mark (C = admm_chains: 1 one chain of ranges, 2 two
-  // interleaved chains started together)
-  const int C = std::min(h->admm_chains, R);
-  bool marked[i7m_handle::kMaxRanges] = {};
-  for (int r = 0; r < R; ++r) {
-    const long lo = cut(r), hi = cut(r + 1);
-    HIPCHK(hipStreamWaitEvent(ss[r], h->ev_order, 0));
+  for (int r = 0; r < 2; ++r) {
+    const long lo = cuts[r], hi = cuts[r + 1];
+    HIPCHK(hipStreamWaitEvent(h->cs[r], h->ev_order, 0));
     if (hi <= lo) continue;
-    if (r >= C && marked[r - C]) HIPCHK(hipStreamWaitEvent(ss[r], h->ev_rmark[r - C], 0));
-    h->mark_ev = r + C < R ? h->ev_rmark[r] : nullptr;
-    const int rc = body(lo, (int)(hi - lo), ss[r]);
-    marked[r] = r + C < R && !h->mark_ev;
-    h->mark_ev = nullptr;
+    if (r == 1 && mark.recorded) HIPCHK(hipStreamWaitEvent(h->cs[1], mark.ev, 0));
+    const int rc = body(lo, (int)(hi - lo), h->cs[r], r == 0 ? &mark : nullptr);
     if (rc) {
       // join the ranges already started back into h->stream before the error returns:
       // the caller's cleanup after a synchronize of h->stream must not race them
       const std::string msg = g_err;
       for (int q = 0; q <= r; ++q) {
-        (void)hipEventRecord(h->ev_rdone[q], ss[q]);
-        (void)hipStreamWaitEvent(h->stream, h->ev_rdone[q], 0);
+        (void)hipEventRecord(h->ev_done[q], h->cs[q]);
+        (void)hipStreamWaitEvent(h->stream, h->ev_done[q], 0);
       }
       g_err = msg;
       return rc;
     }
   }
-  for (int r = 0; r < R; ++r) {
-    HIPCHK(hipEventRecord(h->ev_rdone[r], ss[r]));
-    HIPCHK(hipStreamWaitEvent(h->stream, h->ev_rdone[r], 0));
+  for (int r = 0; r < 2; ++r) {
+    HIPCHK(hipEventRecord(h->ev_done[r], h->cs[r]));
+    HIPCHK(hipStreamWaitEvent(h->stream, h->ev_done[r], 0));
   }
   return I7M_OK;
 }
@@ -1469,30 +1258,12 @@ int i7m_solve_device(i7m_handle* h, int32_t B, const double* d_xu_in, const doub
   if (!d_xu_in || !d_xcur || !d_goals || !d_xu_out) return fail(I7M_EINVAL, "null device pointer");
   HIPCHK(hipSetDevice(h->dev));
   ProblemStats* st = d_stats ? reinterpret_cast<ProblemStats*>(d_stats) : h->d_stats;
-  if (stagger_applies(h, B)) {
+  if (stagger_applies(h->tune, h->cfg.qp_mode, B)) {
     const size_t T = 18 * (size_t)h->cfg.N - 6, N = h->cfg.N;
-    return run_staggered(h, B, [&](long lo, int n, hipStream_t s) {
+    return run_staggered(h, B, [&](long lo, int n, hipStream_t s, StaggerMark* mark) {
       return run_sqp(h, n, d_xu_in + lo * T, d_xu_out + lo * T, d_xcur + lo * 12, d_goals + lo * N * goal_stride,
-                     goal_stride, st + lo, lo, s);
+                     goal_stride, st + lo, lo, s, mark);
     });
-  }
-  if (h->dev_ranges > 1 && B >= h->dev_ranges) {
-    // A/B knob (I7M_DEV_RANGES): the batch as contiguous ranges on the two chunk streams, so one
-    // range's kernels can fill the SIMDs another range's kernel tail leaves idle
-    const size_t T = 18 * (size_t)h->cfg.N - 6, N = h->cfg.N;
-    HIPCHK(hipEventRecord(h->ev_order, h->stream));
-    for (int c = 0; c < 2; ++c) HIPCHK(hipStreamWaitEvent(h->cs[c], h->ev_order, 0));
-    for (int i = 0; i < h->dev_ranges; ++i) {
-      const long lo = (long)B * i / h->dev_ranges, hi = (long)B * (i + 1) / h->dev_ranges;
-      if ((rc = run_sqp(h, (int)(hi - lo), d_xu_in + lo * T, d_xu_out + lo * T, d_xcur + lo * 12,
-                        d_goals + lo * N * goal_stride, goal_stride, st + lo, lo, h->cs[i & 1])))
-        return rc;
-    }
-    for (int c = 0; c < 2; ++c) {
-      HIPCHK(hipEventRecord(h->ev_done[c], h->cs[c]));
-      HIPCHK(hipStreamWaitEvent(h->stream, h->ev_done[c], 0));
-    }
-    return I7M_OK;
   }
   return run_sqp_graphed(h, B, d_xu_in, d_xu_out, d_xcur, d_goals, goal_stride, st);
 }
@@ -1505,7 +1276,7 @@ int i7m_solve(i7m_handle* h, int32_t B, const double* xu_in, const double* xcur,
   if (!xu_in || !xcur || !goals || !xu_out) return fail(I7M_EINVAL, "null pointer");
   HIPCHK(hipSetDevice(h->dev));
   const size_t T = 18 * (size_t)h->cfg.N - 6, N = h->cfg.N;
-  const int nch = std::min(h2h_chunks_for(h, B), B);
+  const int nch = h2h_chunks_for(h->tune, h->cfg.qp_mode, B);
   if (nch > 1) return solve_h2h_chunked(h, B, xu_in, xcur, goals, goal_stride, xu_out, stats, nch);
   if ((rc = copy_in(h, h->d_xu, xu_in, (size_t)B * T))) return rc;
   if ((rc = copy_in(h, h->d_xs, xcur, (size_t)B * 12))) return rc;
@@ -1795,12 +1566,13 @@ int i7m_mpc_run(i7m_handle* h, int32_t B, const double* xstart, const double* en
     HIPCHK(hipMemsetAsync(h->d_xu, 0, 8 * (size_t)B * T, h->stream));
     // the instances [lo, lo + n) through every MPC step on stream s (the whole batch on the
     // handle's stream, or, where the solve staggers, each range on its own: the instances are
-    // independent, so a range runs its steps without waiting for the other)
-    auto loop = [&](long lo, int n, hipStream_t s) -> int {
+    // independent, so a range runs its steps without waiting for the other; its first solve
+    // records the staggered ranges' mark)
+    auto loop = [&](long lo, int n, hipStream_t s, StaggerMark* mark) -> int {
       const double* xu0 = h->d_xu + lo * T;
       double *xu = h->d_xu + lo * T, *out = h->d_out + lo * T, *xs = h->d_xs + lo * 12, *g = h->d_goal + lo * 3 * N;
       int rc3;
-      if ((rc3 = run_sqp(h, n, xu0, xu, xs, g, 3, h->d_stats + lo, lo, s))) return rc3;
+      if ((rc3 = run_sqp(h, n, xu0, xu, xs, g, 3, h->d_stats + lo, lo, s, mark))) return rc3;
       for (int i = 0; i < num_steps; ++i) {
         hipLaunchKernelGGL(k_mpc_goal, dim3((n + 255) / 256), dim3(256), 0, s, h->d_model, n, N, xs, g, d_ep, n_endpoints,
                            d_gi + lo, d_alive + lo, d_dist + (size_t)i * B + lo);
@@ -1813,9 +1585,9 @@ int i7m_mpc_run(i7m_handle* h, int32_t B, const double* xstart, const double* en
       }
       return I7M_OK;
     };
-    if (stagger_applies(h, B)) {
+    if (stagger_applies(h->tune, h->cfg.qp_mode, B)) {
       if ((rc2 = run_staggered(h, B, loop))) return rc2;
-    } else if ((rc2 = loop(0, B, h->stream))) {
+    } else if ((rc2 = loop(0, B, h->stream, nullptr))) {
       return rc2;
     }
     if (num_steps > 0) {

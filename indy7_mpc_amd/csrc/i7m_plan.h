@@ -1,0 +1,212 @@
+// i7m_plan.h — the launch plan of libindy7mpc.so as pure host code: which kernel variant a launch
+// of a given size runs, whether a batch staggers, where its ranges and chunks begin.  No HIP here
+// (tests/host/plan_check.cpp compiles it with a plain C++17 compiler); i7m_api.hip asks these
+// selectors and only launches.
+#pragma once
+
+#include <algorithm>
+#include <cstdlib>
+#include <cstring>
+#include <string>
+
+#include "../../include/indy7_mpc.h"
+
+namespace i7m {
+
+// The launch knobs of a handle: i7m_config's, overridden by the environment (tuning_from_env).
+struct Tuning {
+  int ls_waves = 0;  // waves per problem in k_linesearch: 0 automatic (4 for B <= 768), else I7M_LS_WAVES (1, 2 or 4)
+  // I7M_LS_TAIL = r > 0: split line search — the first launch (one wave per problem) stops after r
+  // rounds, a second launch with two waves per problem finishes the unresolved problems
+  int ls_tail = 0;
+  bool use_graph = false;  // I7M_GRAPH=1: capture the solve once per buffer set, replay it
+                           // (measured 4-5 us slower per solve at B = 1 and 64, level at 4096)
+  int ric_w2 = -1;               // k_riccati_mfma_w2 (two waves per problem): 1 / 0, -1 = by batch size
+  int ric_bc = -1;               // k_riccati_mfma broadcast variant (BC bits), -1 = by batch size
+  // host-to-host i7m_solve split into chunks on two streams, so the copies of one chunk overlap
+  // the solve of another (0 = automatic, h2h_chunks_for; I7M_H2H_CHUNKS or cfg.h2h_chunks)
+  int h2h_chunks = 0;
+  // pipelined host-to-host chunks (h2h_pipe 1 / 2; I7M_H2H_PIPE=0: the first cut's two alternating
+  // streams): per chunk, copy-in on cs[0] -> solve -> copy-out on cs[1]
+  // 2 (default): the chunks' solves alternate over two streams, so one chunk's solve may overlap the
+  // next one's start; 1: all solves on the handle's stream (A/B); 3: as 2, with the
+  // copies out issued by a second host thread (pageable copies block the issuing thread)
+  int h2h_pipe = 2;
+  int h2h_taper = 1;  // I7M_H2H_TAPER=0: equal chunks (A/B)
+  // ADMM mode, i7m_solve_device with B >= admm_stagger_min_b: the batch as two ranges on
+  // streams of their own, the second started once the first has passed a mark (1: its first QP's
+  // scaling and factor; 2: its first QP), so one range's latency-bound phases (the factor, the
+  // OSQP iterations after the first termination check) overlap the other's stream-bound ones
+  // (DESIGN.md §4.7).  0: one range.  I7M_ADMM_STAGGER, I7M_ADMM_STAGGER_MIN_B.
+  int admm_stagger = 1;
+  int admm_stagger_min_b = 3072;  // measured, two ranges: B = 8192 / 4096 / 3072 +9 / +17 / +5 %; 2048 / 1024 -8 / -11 %
+  // k_admm_iter2 (two problems per wave) for launches of at most 512 problems: 3.5 % shorter at
+  // B <= 256, level at 1 024, 19-32 % longer at 4 096 (profiles/r06p, r06q); I7M_ADMM_ITER2 = 0
+  // never, 1 always, -1 (default) by that size
+  int admm_iter2 = -1;
+  // k_admm_iter_res (one problem per workgroup, its records and vectors resident in LDS) for
+  // launches of at most admm_res_max problems at N <= ARES_N without rho adaptation; I7M_ADMM_RES
+  // = 0 never, 1 whenever it fits, -1 (default) by that size
+  int admm_res = -1;
+  int admm_res_max = 256;
+  // k_admm_scale / k_admm_factor as built under the max-ILP scheduler (i7m_admm_prep_tu.hip) for
+  // launches of at most admm_prep_ilp_max problems, else this unit's: 6 % shorter at B <= 256, but
+  // at config 3 (staggered ranges of 2048) the step 0.6 % longer beside the other range's
+  // iteration (profiles/r06zn, r06zo); I7M_ADMM_PREP_ILP = 0 never, 1 always, -1 (default) by size
+  int admm_prep_ilp = -1;
+  int admm_prep_ilp_max = 1024;
+  // box QP: 1 k_ipm_fused<false> (default), 0 I7M_IPM=delta (k_ipm_fused<true>: the corrector
+  // reuses the predictor's factorisation; measured slower), 2 I7M_IPM=split
+  int ipm_mode = 1;
+  int pipeline = I7M_PIPE_AUTO;  // cfg.pipeline, or I7M_PIPE=split|fused|fused_iter
+  bool generic = false;          // I7M_GENERIC=1: the generic kernels even for the baked-in Indy7 model
+};
+
+constexpr int RIC_W2_MAX_B = 128;     // two-wave Riccati up to this batch size (I7M_RIC_W2 forces): 43.9 -> 42.0 us at B = 1, 44.6 -> 42.7 at 64; slower from 512
+// wave priority by progress once Riccati waves share SIMDs: from 768 problems (re-measured in round 3:
+// 55.2 -> 52.4 us at B = 768, 42.5 -> 43.3 at 512; profiles/r03_ric_bc_retune_ab.txt)
+constexpr int RIC_PRIO_MIN_B = 768;
+// waves per problem of the line search (k_linesearch) and of k_sqp_fused
+// (k_linesearch: 4 waves per problem up to 768 problems — re-measured in round 3: 28.2 -> 19.0 us at
+// B = 384, 28.6 -> 19.8 at 512, 29.9 -> 28.8 at 768, 30.6 -> 35.2 at 1024, profiles/r03_ls_waves_ab.txt;
+// k_sqp_fused keeps the 256 it was measured with)
+constexpr int LS_W4_MAX_B = 768, FUSED_W4_MAX_B = 256;
+constexpr int ADMM_ITER2_MAX_B = 512;  // k_admm_iter2 up to this launch size (Tuning::admm_iter2)
+constexpr int ADMM_RES_MAX_N = 32;     // k_admm_iter_res is built for horizons up to this (ARES_N, i7m_admm.h)
+// chunks of a host-to-host solve of B problems: the handle's setting, else automatic — three
+// (tapered) from 3 072 problems, two from 2 048, one piece below (config 3: 1.42 -> 1.21 ms;
+// at B = 1 024 one piece is fastest; DESIGN.md §5 has the A/B)
+constexpr int H2H_3_MIN_B = 3072, H2H_2_MIN_B = 2048;
+
+// Fills *t from the config and the environment: the only getenv site of the knobs above.  False
+// with *err set for a value out of range and for a retired A/B variable, so that an old A/B script
+// does not silently measure the default.
+inline bool tuning_from_env(const i7m_config& cfg, Tuning* t, std::string* err) {
+  for (const char* name : {"I7M_ADMM_CHUNK", "I7M_DEV_RANGES", "I7M_ADMM_CHAINS", "I7M_ADMM_RANGES", "I7M_ADMM_SPLIT",
+                           "I7M_STAGGER_MODES", "I7M_ADMM_ITER_DYN_LDS"})
+    if (std::getenv(name)) {
+      *err = std::string(name) + " is set, but this A/B knob was retired (it measured slower; DESIGN.md has the "
+                                 "numbers): unset it";
+      return false;
+    }
+  *t = Tuning{};
+  if (const char* e = std::getenv("I7M_IPM"))
+    t->ipm_mode = std::strcmp(e, "split") == 0 ? 2 : (std::strcmp(e, "delta") == 0 ? 0 : 1);
+  if (const char* e = std::getenv("I7M_LS_TAIL")) t->ls_tail = std::min(std::max(std::atoi(e), 0), 3);
+  if (const char* e = std::getenv("I7M_LS_WAVES")) t->ls_waves = std::atoi(e) == 4 ? 4 : (std::atoi(e) == 2 ? 2 : 1);
+  if (const char* e = std::getenv("I7M_GRAPH")) t->use_graph = std::atoi(e) != 0;
+  if (const char* e = std::getenv("I7M_RIC_W2")) t->ric_w2 = std::atoi(e) != 0;
+  if (const char* e = std::getenv("I7M_RIC_BC")) {
+    const int v = std::atoi(e) & 7;
+    t->ric_bc = (v == 4 || v == 5) ? (v & 3) : v;  // instantiated: 0 1 2 3 6 7
+  }
+  t->h2h_chunks = cfg.h2h_chunks;
+  if (const char* e = std::getenv("I7M_H2H_CHUNKS")) t->h2h_chunks = std::atoi(e);
+  if (const char* e = std::getenv("I7M_H2H_PIPE")) t->h2h_pipe = std::min(std::max(std::atoi(e), 0), 3);
+  if (const char* e = std::getenv("I7M_H2H_TAPER")) t->h2h_taper = std::atoi(e) != 0;
+  if (const char* e = std::getenv("I7M_ADMM_STAGGER")) {
+    t->admm_stagger = std::min(std::max(std::atoi(e), 0), 4);
+    if (t->admm_stagger > 2) {
+      *err = std::string("I7M_ADMM_STAGGER=") + e + ": the stagger marks 3 and 4 were retired (they measured "
+                                                    "slower; DESIGN.md §4.7): use 0, 1 or 2";
+      return false;
+    }
+  }
+  if (const char* e = std::getenv("I7M_ADMM_STAGGER_MIN_B")) t->admm_stagger_min_b = std::max(std::atoi(e), 2);
+  if (const char* e = std::getenv("I7M_ADMM_ITER2")) t->admm_iter2 = std::min(std::max(std::atoi(e), -1), 1);
+  if (const char* e = std::getenv("I7M_ADMM_RES")) t->admm_res = std::min(std::max(std::atoi(e), -1), 1);
+  if (const char* e = std::getenv("I7M_ADMM_RES_MAX")) t->admm_res_max = std::max(std::atoi(e), 0);
+  if (const char* e = std::getenv("I7M_ADMM_PREP_ILP")) t->admm_prep_ilp = std::min(std::max(std::atoi(e), -1), 1);
+  if (const char* e = std::getenv("I7M_ADMM_PREP_ILP_MAX")) t->admm_prep_ilp_max = std::max(std::atoi(e), 0);
+  if (t->h2h_chunks < 0 || t->h2h_chunks > 64) {
+    *err = "h2h_chunks must be in [0, 64]";
+    return false;
+  }
+  t->pipeline = cfg.pipeline;
+  if (const char* e = std::getenv("I7M_PIPE"))
+    t->pipeline = std::strcmp(e, "fused") == 0 ? I7M_PIPE_FUSED
+                  : std::strcmp(e, "fused_iter") == 0 ? I7M_PIPE_FUSED_ITER
+                  : std::strcmp(e, "split") == 0 ? I7M_PIPE_SPLIT
+                  : t->pipeline;
+  if (const char* e = std::getenv("I7M_GENERIC")) t->generic = std::atoi(e) != 0;
+  return true;
+}
+
+// ---- selectors: Tuning and sizes in, the decision out -------------------------------------------
+
+// The OSQP iteration kernel of a launch of n problems at horizon N: k_admm_iter<true> (rho
+// adaptation), k_admm_iter_res, k_admm_iter2, or k_admm_iter<false> (four problems per wave).
+enum class AdmmIter { adapt, res, iter2, iter4 };
+inline AdmmIter admm_iter_kernel(const Tuning& t, int N, bool adaptive_rho, int n) {
+  if (adaptive_rho) return AdmmIter::adapt;
+  if (N <= ADMM_RES_MAX_N && (t.admm_res > 0 || (t.admm_res < 0 && n <= t.admm_res_max))) return AdmmIter::res;
+  if (t.admm_iter2 > 0 || (t.admm_iter2 < 0 && n <= ADMM_ITER2_MAX_B)) return AdmmIter::iter2;
+  return AdmmIter::iter4;
+}
+
+// the max-ILP-scheduled scaling and factor (i7m_admm_prep_tu.hip) or i7m_api.hip's own?
+inline bool admm_prep_ilp(const Tuning& t, int n) {
+  return t.admm_prep_ilp > 0 || (t.admm_prep_ilp < 0 && n <= t.admm_prep_ilp_max);
+}
+
+// k_riccati_mfma's variant.
+// cross-lane broadcasts (riccati_mfma_body BC): the rollout's and the pivots' by DPP at every
+// batch size; I7M_RIC_BC=0..3 forces one (A/B)
+// DPP pivot broadcasts at every batch size since the round-3 stage changes (re-measured: 57.9 -> 54.7 us
+// at B = 1024, 44.3 -> 42.6 at 512, 41.4 -> 40.0 at 64, 40.7 -> 39.5 at B = 1; before them they
+// cost ~4.5 us below 2048; profiles/r03_ric_bc_retune_ab.txt)
+// wave priority by progress (BC bit 2) once SIMDs hold more than one wave: -6 % at B = 4096,
+// -4 % at B = 1024 (uneven dispatch puts two waves on some SIMDs), +1 us at B = 64
+// small batches: two waves per problem (k_riccati_mfma_w2), the stage's MFMA chains split; not
+// with vout (i7m_qp_value: the one-wave kernel only)
+struct RicVariant {
+  bool w2;
+  int bc;
+};
+inline RicVariant riccati_variant(const Tuning& t, int B, bool vout) {
+  const int bc = t.ric_bc >= 0 ? t.ric_bc : 3 | (B >= RIC_PRIO_MIN_B ? 4 : 0);
+  const bool w2 = !vout && (t.ric_w2 >= 0 ? t.ric_w2 != 0 : B <= RIC_W2_MAX_B);
+  return {w2, bc};
+}
+
+// small batches leave most SIMDs idle: spend them on evaluating every candidate in one round
+inline int ls_waves(const Tuning& t, int B) { return t.ls_waves > 0 ? t.ls_waves : (B <= LS_W4_MAX_B ? 4 : 1); }
+inline int fused_waves(const Tuning& t, int B) { return t.ls_waves > 0 ? t.ls_waves : (B <= FUSED_W4_MAX_B ? 4 : 1); }
+
+// Does this solve run as one k_sqp_fused launch?  (Direct QP only; the box mode's interior point
+// has its own fused kernel between the Riccati and the line search.)  AUTO is the split pipeline
+// at every batch size: the fused one measured 1.1-2.4x slower from B = 1 to 4096.
+inline bool use_fused(const Tuning& t, int qp_mode) {
+  return qp_mode == I7M_QP_DIRECT && (t.pipeline == I7M_PIPE_FUSED || t.pipeline == I7M_PIPE_FUSED_ITER);
+}
+
+// Does a batch of B run as two staggered ranges (Tuning::admm_stagger)?
+inline bool stagger_applies(const Tuning& t, int qp_mode, int B) {
+  return qp_mode == I7M_QP_ADMM && t.admm_stagger > 0 && B >= t.admm_stagger_min_b;
+}
+// The staggered ranges are [0, cut) and [cut, B): half the batch, rounded up to k_admm_iter's four
+// problems per wave and clamped to the batch (the rounded split of a small B must not
+// run past it); an empty second range is skipped.
+inline long stagger_cut(int B) { return std::min<long>(((long)(B / 2) + 3) / 4 * 4, B); }
+
+// How many chunks a host-to-host solve of B problems runs in.
+inline int h2h_chunks_for(const Tuning& t, int qp_mode, int B) {
+  int n;
+  if (t.h2h_chunks > 0) n = t.h2h_chunks;
+  // ADMM mode where the device solve staggers: two chunks, the second's solve behind the first's
+  // mark (solve_h2h_pipelined_body), i.e. the staggered halves with the copies overlapped
+  else if (stagger_applies(t, qp_mode, B)) n = 2;
+  else n = B >= H2H_3_MIN_B ? 3 : (B >= H2H_2_MIN_B ? 2 : 1);
+  return std::min(n, B);
+}
+// First problem of chunk i of nch (i = nch: B).
+// taper (default; I7M_H2H_TAPER=0 for equal chunks): the first and the last chunk half the size
+// of the others, so the copy-in before the first solve and the copy-out after the last are short
+inline long chunk_lo(int B, int nch, int i, bool taper) {
+  if (!taper || nch < 3) return (long)B * i / nch;
+  if (i == 0) return 0;
+  if (i == nch) return B;
+  return (long)((double)B * (2 * i - 1) / (2.0 * (nch - 1)));
+}
+
+}  // namespace i7m

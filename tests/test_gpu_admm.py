@@ -397,3 +397,71 @@ def test_admm_iteration_kernels_bit_identical(lib, model, monkeypatch, B, N, adm
     for other in res[1:]:
         for a, b in zip(res[0], other):
             np.testing.assert_array_equal(a, b)
+
+
+def _two_solves(lib, model, B, N, batch, device):
+    """Two consecutive ADMM solves on a fresh handle (the second from the first's output and OSQP
+    state), through i7m_solve_device (torch device pointers) or i7m_solve: the outputs, the carried
+    state, the OSQP records with statuses, and the duals."""
+    xcur, goals, XU = batch
+    h = lib.Handle(model, N=N, max_batch=B, qp_mode=lib.QP_ADMM)
+    outs = []
+    if device:
+        import torch
+        dev = torch.device("cuda", 0)
+        t_xu, t_xs, t_g = (torch.from_numpy(np.ascontiguousarray(x)).to(dev) for x in (XU, xcur, goals))
+        for call in range(2):
+            t_out = torch.empty_like(t_xu)
+            torch.cuda.synchronize()
+            h.solve_device(B, t_xu.data_ptr(), t_xs.data_ptr(), t_g.data_ptr(), 3, t_out.data_ptr())
+            h.synchronize()
+            outs.append(t_out.cpu().numpy())
+            t_xu = t_out
+    else:
+        xin = XU
+        for call in range(2):
+            xin, _ = h.solve(xcur, goals, xin)
+            outs.append(xin)
+    res = tuple(outs) + h.admm_state(B) + h.admm_stats(B, with_status=True) + (h.admm_dual(B),)
+    h.close()
+    return res
+
+
+@pytest.mark.parametrize("B", [2, 5, 13])
+def test_admm_stagger_small_batches(lib, model, monkeypatch, B):
+    """The staggered ranges at batch sizes where the rounded cut meets the batch's end
+    (I7M_ADMM_STAGGER_MIN_B = 2): B = 2 leaves the second range empty (cut 4 clamped to 2), B = 5
+    splits 4 + 1, B = 13 splits 8 + 5.  With the mark after the first QP's scaling + factor
+    (I7M_ADMM_STAGGER 1) and after the first QP (2), i7m_solve_device's two ranges and i7m_solve's
+    two chunks give a one-range handle's (0) results bit for bit over two consecutive solves: XU,
+    the OSQP state, iteration records, statuses and duals."""
+    N = 16
+    batch = synthetic_batch(B, N, 55)
+    monkeypatch.setenv("I7M_ADMM_STAGGER_MIN_B", "2")
+    for device in (True, False):
+        res = {}
+        for mode in ("0", "1", "2"):
+            monkeypatch.setenv("I7M_ADMM_STAGGER", mode)
+            res[mode] = _two_solves(lib, model, B, N, batch, device)
+        assert (res["0"][7][:, 0] >= 25).all()  # every problem ran its first QP
+        for mode in ("1", "2"):
+            for a, b in zip(res["0"], res[mode]):
+                np.testing.assert_array_equal(a, b, err_msg=f"stagger {mode} device {device}")
+
+
+@pytest.mark.parametrize("B,N", [(13, 32), (3, 64)])
+def test_admm_prep_variants_bit_identical(lib, model, monkeypatch, B, N):
+    """k_admm_scale / k_admm_factor as built under the max-ILP scheduler (I7M_ADMM_PREP_ILP 1) and
+    under the default one (0) run the same arithmetic: two consecutive solves are equal bit for bit,
+    carried state, OSQP records and statuses included.  N = 64 reaches k_admm_scale<18>."""
+    xcur, goals, XU = synthetic_batch(B, N, 54)
+    res = []
+    for ilp in ("1", "0"):
+        monkeypatch.setenv("I7M_ADMM_PREP_ILP", ilp)
+        h = lib.Handle(model, N=N, max_batch=B, qp_mode=lib.QP_ADMM)
+        o1, _ = h.solve(xcur, goals, XU)
+        o2, _ = h.solve(xcur, goals, o1)
+        res.append((o1, o2) + h.admm_state(B) + h.admm_stats(B, with_status=True))
+        h.close()
+    for a, b in zip(res[0], res[1]):
+        np.testing.assert_array_equal(a, b)

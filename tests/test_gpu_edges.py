@@ -163,6 +163,18 @@ def test_release_library_refuses_ablation_knob(lib, model, monkeypatch):
     lib.Handle(model, N=16).close()
 
 
+@pytest.mark.parametrize("name,value", [("I7M_ADMM_CHUNK", "1024"), ("I7M_ADMM_RANGES", "4"), ("I7M_ADMM_STAGGER", "3")])
+def test_retired_ab_knob_is_refused(lib, model, monkeypatch, name, value):
+    """A retired A/B variable (csrc/i7m_plan.h tuning_from_env; the full list is checked on the host,
+    tests/host/plan_check.cpp) fails i7m_create with a message naming it, so an old A/B script does
+    not silently measure the default."""
+    monkeypatch.setenv(name, value)
+    with pytest.raises(lib.I7MError, match=name + ".*retired"):
+        lib.Handle(model, N=16, qp_mode=lib.QP_ADMM)
+    monkeypatch.delenv(name)
+    lib.Handle(model, N=16, qp_mode=lib.QP_ADMM).close()
+
+
 def test_reset_and_wrench_clear_with_captured_graphs(lib, model, monkeypatch):
     """i7m_reset keeps results (the exact solve has no warm start) and the wrench; clearing the
     wrench afterwards must not replay a graph captured with the wrench kernels (I7M_GRAPH=1)."""
