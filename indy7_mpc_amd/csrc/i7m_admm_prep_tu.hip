@@ -7,9 +7,9 @@
 // i7m_api.hip keeps its own default-scheduled copies for the staggered ranges of config 3, where
 // these make the step 0.6 % longer (profiles/r06zo; Tuning::admm_prep_ilp of i7m_plan.h picks by size).
 //
-// i7m_admm.h included inside an anonymous namespace: this unit's kernels and device functions stay
-// internal (I7M_ADMM_PREP_ONLY: no copies of the iteration kernels).  The launcher is the only
-// external symbol, with builtin parameter types only.
+// i7m_admm.h (the preparation alone: the iteration kernels are i7m_admm_iter.h) included inside an
+// anonymous namespace: this unit's kernels and device functions stay internal.  The launcher is the
+// only external symbol, with builtin parameter types only.
 #include <hip/hip_runtime.h>
 #include <hip/hip_ext.h>
 
@@ -18,7 +18,6 @@
 
 #include "../../include/indy7_mpc.h"
 
-#define I7M_ADMM_PREP_ONLY 1
 namespace {
 #include "i7m_admm.h"
 }  // namespace

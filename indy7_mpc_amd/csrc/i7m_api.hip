@@ -22,7 +22,7 @@
 #include "i7m_linearize.h"
 #include "i7m_riccati_mfma.h"
 #include "i7m_box.h"
-#include "i7m_admm.h"
+#include "i7m_admm_iter.h"
 #include "i7m_mpc.h"
 #include "i7m_plan.h"
 
@@ -471,7 +471,7 @@ int solve_qp(i7m_handle* h, hipStream_t s, const Bufs& W, const SolveParams& P, 
              const int* active, double* sol, const double** out, int sqp_iter = 0, StaggerMark* mark = nullptr) {
   int rc;
   if (h->cfg.qp_mode == I7M_QP_ADMM) {
-    // OSQP's iteration from the problems' carried state (i7m_admm.h; oracle/osqp_admm.py)
+    // OSQP's iteration from the problems' carried state (i7m_admm_iter.h; oracle/osqp_admm.py)
     *out = sol;
     if (P.B == 0) return I7M_OK;
     AdmmArgs a = W.adm;

@@ -72,7 +72,7 @@ constexpr int RIC_PRIO_MIN_B = 768;
 // k_sqp_fused keeps the 256 it was measured with)
 constexpr int LS_W4_MAX_B = 768, FUSED_W4_MAX_B = 256;
 constexpr int ADMM_ITER2_MAX_B = 512;  // k_admm_iter2 up to this launch size (Tuning::admm_iter2)
-constexpr int ADMM_RES_MAX_N = 32;     // k_admm_iter_res is built for horizons up to this (ARES_N, i7m_admm.h)
+constexpr int ADMM_RES_MAX_N = 32;     // k_admm_iter_res is built for horizons up to this (ARES_N, i7m_admm_iter.h)
 // chunks of a host-to-host solve of B problems: the handle's setting, else automatic — three
 // (tapered) from 3 072 problems, two from 2 048, one piece below (config 3: 1.42 -> 1.21 ms;
 // at B = 1 024 one piece is fastest; DESIGN.md §5 has the A/B)

@@ -2,7 +2,9 @@
 // each instrumented kernel's waves record [start, end] (s_memrealtime, the 100 MHz device-wide
 // clock), the hardware slot they ran on (HW_ID, XCC_ID) and the kernel / workgroup, so a tool can
 // see how a launch's waves were spread over the 1024 SIMDs and how much of the launch each SIMD
-// sat idle (load imbalance, tails).  The release library compiles I7M_TL to nothing.
+// sat idle (load imbalance, tails); and cycle stamps inside one ADMM kernel (I7M_STAMP,
+// tl_write_stamps; tools/step_stamps.py).  The release library compiles I7M_TL and I7M_STAMP to
+// nothing.
 //
 // Buffer layout (device, u64): [0] unused, [1] capacity (records), [2..7] unused, then 4 u64 per
 // record: t_start, t_end, HW_ID | XCC_ID << 32, kernel id | workgroup << 8.  Record slot =
@@ -49,8 +51,31 @@ static inline int tl_set(void* p) {
   return hipMemcpyToSymbol(HIP_SYMBOL(g_tl), &v, sizeof(v)) == hipSuccess ? 0 : -1;
 }
 
+// Cycle stamps inside one kernel (tools/step_stamps.py): s_memtime (the shader clock) between
+// sched barriers, waited for, kept in `arr[i]` when `on`.  The stamps fence the schedule and drain
+// LDS reads: read the shares, not the length.
+#define I7M_STAMP(arr, i, on)                                                   \
+  do {                                                                          \
+    __builtin_amdgcn_sched_barrier(0);                                          \
+    unsigned long long v_;                                                      \
+    asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(v_)::"memory"); \
+    __builtin_amdgcn_sched_barrier(0);                                          \
+    if (on) (arr)[i] = v_;                                                      \
+  } while (0)
+// ... written by one lane to record area 5 (kernel id 5's first slots): r[0..8] the stamps (zero
+// past the n taken), r[9] the I7M_ABLATE tag, r[10] the layout: 0 the streaming OSQP iteration
+// kernels, 1 the resident one, 2 the factor, 3 the scaling.
+__device__ __forceinline__ void tl_write_stamps(const unsigned long long* stamps, int n, int ablate, int layout) {
+  if (!g_tl) return;
+  unsigned long long* r = g_tl + 8 + 4 * (5ull << 16);
+  for (int i = 0; i < 9; ++i) r[i] = i < n ? stamps[i] : 0;
+  r[9] = (unsigned long long)ablate;
+  r[10] = (unsigned long long)layout;
+}
+
 }  // namespace i7m
 #define I7M_TL(kid) i7m::TlScope i7m_tl_scope_(kid)
 #else
 #define I7M_TL(kid)
+#define I7M_STAMP(arr, i, on)
 #endif

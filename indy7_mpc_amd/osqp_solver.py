@@ -3,7 +3,7 @@
 Same constructor, attributes and methods.  The numbers come from the GPU:
   * ``setup_and_solve_qp`` linearises on the device (k_linearize) and, by default
     (``qp_mode="admm"``), runs OSQP's own algorithm on it (k_admm_scale, k_admm_factor,
-    k_admm_iter; i7m_admm.h) from a warm-started per-problem OSQP state, as the reference's
+    k_admm_iter; i7m_admm.h, i7m_admm_iter.h) from a warm-started per-problem OSQP state, as the reference's
     ``self.osqp`` object does (:38-40, 140-143): the trajectories are the reference's own
     (oracle/osqp_admm.py pins them against the notebook's printed closed loop).
     ``qp_mode="direct"`` instead solves each QP EXACTLY with the block-tridiagonal Riccati kernel

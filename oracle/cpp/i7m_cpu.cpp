@@ -1102,7 +1102,7 @@ struct Solver {
   //   forward   g_k = rhs_k - [re I_k (J_{k-1} h_{k-1}); 0],  h_k = Linv_k' (Linv_k g_k)
   //   backward  xt_k = h_k - Linv_k' (Linv_k (J_k' (re I_{k+1} xt_{k+1}[:12])))
   // every product an fma chain over its 18 (or 12) terms in ascending order, as the device's
-  // sweeps (indy7_mpc_amd/csrc/i7m_admm.h, k_admm_iter).  (An explicit S_k^-1 instead of the
+  // sweeps (indy7_mpc_amd/csrc/i7m_admm_iter.h, k_admm_iter).  (An explicit S_k^-1 instead of the
   // triangular pair reads the same bytes but lost 5 orders of accuracy on the ill-conditioned M of
   // a second SQP iteration, cond ~4e7: forward error 1e-5 vs 3e-10)
   std::vector<double> aLinv;  // (N, 18, 18) Linv_k, zeros above the diagonal and in the last knot's padding
@@ -1175,7 +1175,7 @@ struct Solver {
   }
   // compact J_k entry (i, j) (the dense 12 x 18 block; the device reads it from its record)
   double Jkc(int k, int i, int j) const { return aJ[216 * k + 18 * i + j]; }
-  // The device's dot products (indy7_mpc_amd/csrc/i7m_admm.h a4_dot16 / a4_dot6, here adm_dot16 / adm_dot6): 16 terms as four
+  // The device's dot products (indy7_mpc_amd/csrc/i7m_admm_iter.h a4_dot16 / a4_dot6, here adm_dot16 / adm_dot6): 16 terms as four
   // interleaved fma chains (l mod 4) combined (a0 + a1) + (a2 + a3); 6 terms as two (r even, odd)
   static double adm_dot16(const double* cf, const double* v) {
     double a[4] = {0.0, 0.0, 0.0, 0.0};

@@ -4,7 +4,8 @@
     python tools/lib_diff.py cmp A.npz B.npz
 
 dump: one config-3 solve (B = 4096, N = 32, bench.py's draws), one config-4 solve (B = 256,
-N = 64, box rows) and the notebook's 500-step closed loop (B = 1, N = 32).
+N = 64, box rows), the notebook's 500-step closed loop (B = 1, N = 32), and the ADMM mode: config
+3, N = 64, odd batches, adaptive rho, the closing tests after max_iter, each streaming kernel forced.
 cmp: per output, how many problems differ at all, the largest relative difference, and for the
 closed loop the first step at which the goal distances differ.
 """
@@ -51,6 +52,33 @@ def dump(path):
     h = _lib.Handle(m, N=32, max_batch=1, qp_mode=_lib.QP_ADMM)
     out["mpca"] = h.mpc_run(np.array([tr["xstart"]]), ends, 40)[0][:, 0]
     h.close()
+    # the iteration kernels' other paths, B = 13 (idle rows in the streaming kernels' last wave): the
+    # adaptive-rho kernel with its in-kernel re-factor, the closing tests after max_iter, and each
+    # streaming kernel forced at N = 32 (and with the closing tests: `close` alone runs the resident
+    # kernel); outputs, carried state, rho, OSQP iterations and statuses
+    it2, it4 = {"I7M_ADMM_RES": "0", "I7M_ADMM_ITER2": "1"}, {"I7M_ADMM_RES": "0", "I7M_ADMM_ITER2": "0"}
+    closing = dict(max_iter=20, eps_abs=1e-3, eps_rel=1e-3)
+    for key, N, admm, env in (("adapt", 16, dict(rho=0.005, adaptive_rho_interval=25), {}),
+                              ("close", 16, closing, {}), ("it2", 32, None, it2), ("it4", 32, None, it4),
+                              ("close2", 16, closing, it2), ("close4", 16, closing, it4)):
+        xc, g, xu = synthetic_batch(13, N, 54)
+        saved = {k: os.environ.get(k) for k in env}
+        os.environ.update(env)
+        try:  # (the handle reads the forced kernel choice when it is created)
+            h = _lib.Handle(m, N=N, max_batch=13, qp_mode=_lib.QP_ADMM, **({"admm": admm} if admm else {}))
+        finally:
+            for k, v in saved.items():
+                if v is None:
+                    os.environ.pop(k, None)
+                else:
+                    os.environ[k] = v
+        o1 = h.solve(xc, g, xu)[0]
+        o2 = h.solve(xc, g, o1)[0]
+        state, (its, rho, stat) = h.admm_state(13), h.admm_stats(13, with_status=True)
+        out[key] = np.concatenate([o1, o2], axis=1)
+        out[key + "_state"] = np.concatenate(state[:4] + (state[4][:, None], rho[:, None]), axis=1)
+        out[key + "_stats"] = np.concatenate([its, stat], axis=1)
+        h.close()
     out["ver"] = np.array(_lib.version())
     np.savez(path, **out)
 
@@ -58,7 +86,8 @@ def dump(path):
 def cmp(a, b):
     A, B = np.load(a), np.load(b)
     print("A:", str(A["ver"]), "\nB:", str(B["ver"]))
-    for k in ("c3", "c4", "a3", "a3_state", "a3_iters", "a64", "a64_state", "a13", "a13_state"):
+    for k in ("c3", "c4", "a3", "a3_state", "a3_iters", "a64", "a64_state", "a13", "a13_state") + tuple(
+            k + s for k in ("adapt", "close", "it2", "it4", "close2", "close4") for s in ("", "_state", "_stats")):
         if k not in A or k not in B:
             continue
         x, y = A[k].astype(float), B[k].astype(float)

@@ -4,7 +4,7 @@
 // fma's, the lanes a later fma masks out get back the accumulator as that fma read it, before the
 // previous fma's write landed — they lose their earlier terms (lane 13, in bank 3, keeps all
 // four and is right).  With `s_nop 1` (the DPP read's two wait states) between them every lane
-// is right.  The four-chain forms of i7m_admm.h never meet this: a chain's next fma is four
+// is right.  The four-chain forms of i7m_admm_iter.h never meet this: a chain's next fma is four
 // instructions behind its last.
 // Build: hipcc --offload-arch=gfx950 -O3 -std=c++17 tools/probes/rowsplit_probe.hip -o tools/probes/rowsplit_probe
 #include <hip/hip_runtime.h>
