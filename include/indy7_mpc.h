@@ -35,6 +35,9 @@
  *   i7m_set_external_wrench    batch_sqp.set_external_wrench_batch  gato_controller.py:129
  *   i7m_mpc_run                MPC_OSQP.run_mpc over B instances     src/osqp_mpc.py:14-72
  *                              (batch axis of src/gato_mpc_batch.py:76-217)
+ *   i7m_mpc_run_sampled        MPC_GATO_Batch_Sample.run_mpc over G controllers of H wrench
+ *                              hypotheses       src/gato_mpc_batch_sample.py:106-300
+ *                              (find_best_idx / resample_f_ext_batch, gato_controller.py:109-129)
  *
  * Layouts (all fp64, C-contiguous, row = problem):
  *   XU    (B, T)  T = 18N-6, [x_0,u_0,x_1,u_1,...,x_{N-1}], x=[q(6),v(6)]  src/osqp_solver.py:22
@@ -310,6 +313,66 @@ int i7m_rk4(i7m_handle* h, int32_t Bq, const double* q, const double* v, const d
  * external wrench set (MPC_OSQP's loop has none, src/osqp_mpc.py:56). */
 int i7m_mpc_run(i7m_handle* h, int32_t B, const double* xstart, const double* endpoints, int32_t n_endpoints,
                 int32_t num_steps, double* dist_out, double* q_out, double* xcur_out, double* xu_out);
+
+/* Options of i7m_mpc_run_sampled; fill with i7m_sampled_opts_default, then change fields. */
+typedef struct i7m_sampled_opts {
+  double sim_dt;        /* the plant's and the scoring's one rk4 step per MPC step, 0 < sim_dt <= dt;
+                           default 0.001 (src/gato_mpc_batch_sample.py:106) */
+  double decay;         /* the resampled hypotheses are scaled by this; default 1 (0.97: gato_controller.py:128) */
+  int32_t frame;        /* I7M_WRENCH_* of fhyp, f_actual and the wrench left on the handle; default WORLD */
+  int32_t reset_what;   /* I7M_QP_ADMM: I7M_ADMM_RESET_* bits applied to every row before each step's
+                           solve; default ALL (the reference's reset() + resetRho(), :222-223); 0
+                           carries the OSQP state from step to step */
+  int32_t keep_best;    /* resample: the winning row keeps the winning wrench; default 0 */
+  int32_t n_actual;     /* f_actual is (n_actual, G, 6): 1 (held for the run) or num_steps; default 1 */
+} i7m_sampled_opts;
+int i7m_sampled_opts_default(i7m_sampled_opts* opts);
+
+/* Sampled-wrench closed loop of G independent controllers with H wrench hypotheses each on the
+ * device: MPC_GATO_Batch_Sample.run_mpc (src/gato_mpc_batch_sample.py:106-300) with the
+ * controller's selection and resampling rule (gato_controller.py:109-129).  The B = G H problem
+ * rows are laid out so that group g owns rows [g H, (g + 1) H); H in {1, 2, 4, ..., 256} (the
+ * SQPSolverfloat_* sizes), B <= max_batch.
+ *   init    goal = endpoints[0] tiled; XU rows = 0 but XU[:, :12] = xstart[g] (:124-126); the rows'
+ *           wrenches = fhyp (B, 6) in opts->frame; the solver state afresh; XU_new = sqp(rows);
+ *           XU_best[g] = XU_new[g H] (:127-128)
+ *   step i, every group still running:
+ *     plant    x_last = xcur[g], u_last = XU_best[g][12:18]; xcur[g] = rk4(x_last, u_last, sim_dt,
+ *              f_actual[i or 0][g]) (:163-178): one step, a world wrench converted once at
+ *              x_last's q as i7m_rk4 does; q_out[i, g] = xcur[g][:6]
+ *     spread   every row of g: xcur_row = xcur[g], XU_row = [xcur[g], XU_best[g][12:]] (:190-193;
+ *              no warm-start shift: the reference's is commented out)
+ *     goal     d = |eepos(xcur q) - goal|, dist_out[i, g] = d; d < 0.095: the next endpoint (not
+ *              cyclic, :208-214), or at the last endpoint the group stops here (:215-217)
+ *     reset    I7M_QP_ADMM: opts->reset_what on every row
+ *     solve    XU_new = sqp(rows), each row under its own hypothesis wrench
+ *     select   err_h = |rk4(x_last, u_last, sim_dt, wrench row h) - xcur[g]|_2 over all 12 entries;
+ *              best = the lowest index among the minima (:287's `<`; a NaN error never wins, all
+ *              NaN -> 0); best_out[i, g] = best, fbest_out[i, g] = wrench row best, XU_best[g] =
+ *              XU_new[g H + best].  Plant and scoring run the same code, so a hypothesis equal to
+ *              the actual wrench scores exactly 0.
+ *     resample only with noise (num_steps, B, 3), in gato_controller.py:120-129's order: rows =
+ *              f_best; rows[:, :3] += noise[i]; if keep_best: row[best] = f_best; rows[:, 3:] = 0;
+ *              row[0] = 0; rows *= decay.  (keep_best = 1, decay = 0.97: the controller's rule;
+ *              keep_best = 0, decay = 1: src/gato_mpc_batch_sample.py:291-298.)
+ * A group that stopped at step i has best_out[i] = -1 and fbest_out[i] = NaN (no selection was
+ * made), and from step i + 1 on dist_out / q_out / fbest_out are NaN and best_out is -1.
+ * Deliberately not reproduced: the reference splits a plant step at a knot boundary (:170-187),
+ * which with one step of sim_dt <= dt and no shift never happens (the plant stays in knot 0); and
+ * it random-walks the actual force (:244-250), where here the caller supplies the schedule
+ * f_actual (opts->n_actual, G, 6).
+ * xstart (G, 12), endpoints (E, 3); noise may be NULL (no resampling); opts NULL = the defaults.
+ * Outputs: dist_out (num_steps, G) required; best_out (num_steps, G) int32, q_out and fbest_out
+ * (num_steps, G, 6), xcur_out (G, 12), xu_best_out (G, T) the final XU_best, fhyp_out (B, 6) the
+ * final hypotheses: each may be NULL.  Synchronous.  I7M_QP_DIRECT and I7M_QP_ADMM; I7M_EINVAL
+ * before any work for I7M_QP_BOX, another H, G H > max_batch, sim_dt outside (0, dt] and null
+ * required pointers.  After the run the handle's external wrench is the final hypothesis set in
+ * opts->frame (as after i7m_set_external_wrench(h, B, fhyp_out, frame)): i7m_mpc_run keeps
+ * refusing the handle until it is cleared. */
+int i7m_mpc_run_sampled(i7m_handle* h, int32_t G, int32_t H, const double* xstart, const double* endpoints,
+                        int32_t n_endpoints, int32_t num_steps, const double* fhyp, const double* f_actual,
+                        const double* noise, const i7m_sampled_opts* opts, double* dist_out, int32_t* best_out,
+                        double* q_out, double* fbest_out, double* xcur_out, double* xu_best_out, double* fhyp_out);
 
 /* Per-kernel device timing with HIP events on the launch stream. */
 enum { I7M_K_LIN = 0, I7M_K_RICCATI = 1, I7M_K_LINESEARCH = 2, I7M_K_RICCATI_BOX = 3, I7M_K_IPM = 4, I7M_K_IPM_FUSED = 5,

@@ -117,7 +117,19 @@ STATS_DTYPE = np.dtype(
 )
 assert STATS_DTYPE.itemsize == C.sizeof(i7m_problem_stats)
 
+class i7m_sampled_opts(C.Structure):
+    _fields_ = [
+        ("sim_dt", C.c_double),
+        ("decay", C.c_double),
+        ("frame", C.c_int32),
+        ("reset_what", C.c_int32),
+        ("keep_best", C.c_int32),
+        ("n_actual", C.c_int32),
+    ]
+
+
 _DP = C.POINTER(C.c_double)
+_IP32 = C.POINTER(C.c_int32)
 _H = C.c_void_p
 
 # (name, restype, argtypes) — every symbol declared in include/indy7_mpc.h
@@ -151,6 +163,9 @@ SIGNATURES = [
     ("i7m_aba_derivatives", C.c_int, [_H, C.c_int32, _DP, _DP, _DP, _DP, _DP, _DP, _DP]),
     ("i7m_rk4", C.c_int, [_H, C.c_int32, _DP, _DP, _DP, C.c_double, _DP, C.c_int32, _DP, _DP]),
     ("i7m_mpc_run", C.c_int, [_H, C.c_int32, _DP, _DP, C.c_int32, C.c_int32, _DP, _DP, _DP, _DP]),
+    ("i7m_sampled_opts_default", C.c_int, [C.POINTER(i7m_sampled_opts)]),
+    ("i7m_mpc_run_sampled", C.c_int, [_H, C.c_int32, C.c_int32, _DP, _DP, C.c_int32, C.c_int32, _DP, _DP, _DP,
+                                      C.POINTER(i7m_sampled_opts), _DP, _IP32, _DP, _DP, _DP, _DP, _DP]),
     ("i7m_set_timing", C.c_int, [_H, C.c_int]),
     ("i7m_get_kernel_times", C.c_int, [_H, _DP, C.POINTER(C.c_int32), C.c_int32]),
     ("i7m_reset_kernel_times", C.c_int, [_H]),
@@ -436,6 +451,48 @@ class Handle:
         _check(self._lib.i7m_mpc_run(self._h, B, _ptr(xs), _ptr(ep), ep.shape[0], int(num_steps), _ptr(d), _ptr(q),
                                      _ptr(xc), _ptr(xu)))
         return d, q, xc, xu
+
+    def mpc_run_sampled(self, xstart, endpoints, num_steps, fhyp, f_actual, noise=None, sim_dt=0.001, frame="world",
+                        reset_what=ADMM_RESET_ALL, keep_best=False, decay=1.0):
+        """Sampled-wrench closed loop of G controllers with H hypotheses each on the device
+        (i7m_mpc_run_sampled): xstart (G, 12), endpoints (E, 3), fhyp (G * H, 6) with group g owning
+        rows [g H, (g + 1) H), f_actual (G, 6) held for the run or (num_steps, G, 6), noise
+        (num_steps, G * H, 3) or None (no resampling).  Returns a dict: dist (num_steps, G), best
+        (num_steps, G) int32, q and fbest (num_steps, G, 6), xcur (G, 12), xu_best (G, T), fhyp
+        (G * H, 6) the final hypotheses (also left set on the handle, in `frame`)."""
+        xs = _f64(xstart).reshape(-1, NX)
+        ep = _f64(endpoints).reshape(-1, 3)
+        G = xs.shape[0]
+        fh = _f64(fhyp).reshape(-1, 6)
+        if G < 1 or fh.shape[0] % G:
+            raise ValueError(f"fhyp has {fh.shape[0]} rows, not a multiple of the {G} groups")
+        Hn = fh.shape[0] // G
+        num_steps = int(num_steps)
+        fa = _f64(f_actual)
+        if fa.size == G * 6:
+            fa = fa.reshape(1, G, 6)
+        elif fa.size == num_steps * G * 6:
+            fa = fa.reshape(num_steps, G, 6)
+        else:
+            raise ValueError(f"f_actual must be ({G}, 6) or ({num_steps}, {G}, 6)")
+        nz = None
+        if noise is not None:
+            nz = _f64(noise)
+            if nz.size != num_steps * G * Hn * 3:
+                raise ValueError(f"noise must be ({num_steps}, {G * Hn}, 3)")
+        o = i7m_sampled_opts()
+        _check(self._lib.i7m_sampled_opts_default(C.byref(o)))
+        o.sim_dt, o.decay, o.frame = float(sim_dt), float(decay), _FRAMES[frame]
+        o.reset_what, o.keep_best, o.n_actual = int(reset_what), int(bool(keep_best)), fa.shape[0]
+        out = dict(dist=np.empty((num_steps, G)), best=np.empty((num_steps, G), dtype=np.int32),
+                   q=np.empty((num_steps, G, NJ)), fbest=np.empty((num_steps, G, 6)), xcur=np.empty((G, NX)),
+                   xu_best=np.empty((G, self.T)), fhyp=np.empty((G * Hn, 6)))
+        _check(self._lib.i7m_mpc_run_sampled(self._h, G, Hn, _ptr(xs), _ptr(ep), ep.shape[0], num_steps, _ptr(fh),
+                                             _ptr(fa), _ptr(nz) if nz is not None else None, C.byref(o),
+                                             _ptr(out["dist"]), out["best"].ctypes.data_as(_IP32), _ptr(out["q"]),
+                                             _ptr(out["fbest"]), _ptr(out["xcur"]), _ptr(out["xu_best"]),
+                                             _ptr(out["fhyp"])))
+        return out
 
     # ---- timing --------------------------------------------------------------------------
     def set_stream(self, stream_ptr: int):

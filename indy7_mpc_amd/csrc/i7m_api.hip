@@ -24,6 +24,7 @@
 #include "i7m_box.h"
 #include "i7m_admm_iter.h"
 #include "i7m_mpc.h"
+#include "i7m_mpc_sampled.h"
 #include "i7m_plan.h"
 
 // Source hash of the tree this library was built from (__graft_entry__.build passes it), so
@@ -1219,9 +1220,11 @@ extern "C++" {  // (C++ helpers inside the C-ABI block)
 // first has passed its mark (the first run_sqp of its `body` records it; StaggerMark), both
 // forked from and joined back into h->stream.  body(lo, n, stream, mark) enqueues the work of
 // problems [lo, lo + n).  Results are the one-range run's: the problems are independent.
+// cut: where the second range begins; -1 = stagger_cut(B) (a caller whose problems come in groups
+// passes a cut that splits none).
 template <class Body>
-static int run_staggered(i7m_handle* h, int B, Body&& body) {
-  const long cuts[3] = {0, stagger_cut(B), B};
+static int run_staggered(i7m_handle* h, int B, Body&& body, long cut = -1) {
+  const long cuts[3] = {0, cut < 0 ? stagger_cut(B) : cut, B};
   StaggerMark mark{h->ev_rmark, h->tune.admm_stagger, false};
   HIPCHK(hipEventRecord(h->ev_order, h->stream));
   for (int r = 0; r < 2; ++r) {
@@ -1600,6 +1603,183 @@ int i7m_mpc_run(i7m_handle* h, int32_t B, const double* xstart, const double* en
     return I7M_OK;
   };
   rc = run();
+  (void)hipStreamSynchronize(h->stream);
+  cleanup();
+  return rc;
+}
+
+int i7m_sampled_opts_default(i7m_sampled_opts* o) {
+  if (!o) return fail(I7M_EINVAL, "null opts");
+  o->sim_dt = 0.001;  // run_mpc's default, src/gato_mpc_batch_sample.py:106
+  o->decay = 1.0;
+  o->frame = I7M_WRENCH_WORLD;
+  o->reset_what = I7M_ADMM_RESET_ALL;  // reset() + resetRho() before every solve, :222-223
+  o->keep_best = 0;
+  o->n_actual = 1;
+  return I7M_OK;
+}
+
+int i7m_mpc_run_sampled(i7m_handle* h, int32_t G, int32_t H, const double* xstart, const double* endpoints,
+                        int32_t n_endpoints, int32_t num_steps, const double* fhyp, const double* f_actual,
+                        const double* noise, const i7m_sampled_opts* opts, double* dist_out, int32_t* best_out,
+                        double* q_out, double* fbest_out, double* xcur_out, double* xu_best_out, double* fhyp_out) {
+  if (!h) return fail(I7M_EINVAL, "null handle");
+  i7m_sampled_opts o;
+  (void)i7m_sampled_opts_default(&o);
+  if (opts) o = *opts;
+  if (h->cfg.qp_mode == I7M_QP_BOX)
+    return fail(I7M_EINVAL, "mpc_run_sampled: I7M_QP_BOX is not supported (I7M_QP_DIRECT or I7M_QP_ADMM)");
+  if (H < 1 || H > 256 || (H & (H - 1)))
+    return fail(I7M_EINVAL, "mpc_run_sampled: H = " + std::to_string(H) + " is not one of 1, 2, 4, ..., 256");
+  if (G < 0 || (long)G * H > h->cfg.max_batch)
+    return fail(I7M_EINVAL, "mpc_run_sampled: G x H = " + std::to_string((long)G * H) + " rows outside [0, max_batch=" +
+                                std::to_string(h->cfg.max_batch) + "]");
+  if (!(o.sim_dt > 0.0) || !(o.sim_dt <= h->cfg.dt))
+    return fail(I7M_EINVAL, "mpc_run_sampled: sim_dt must be in (0, dt]");
+  if (o.frame != I7M_WRENCH_LOCAL && o.frame != I7M_WRENCH_WORLD)
+    return fail(I7M_EINVAL, "mpc_run_sampled: frame must be I7M_WRENCH_LOCAL or I7M_WRENCH_WORLD");
+  if (o.reset_what & ~I7M_ADMM_RESET_ALL) return fail(I7M_EINVAL, "mpc_run_sampled: unknown I7M_ADMM_RESET_* bits");
+  if (n_endpoints < 1 || num_steps < 0) return fail(I7M_EINVAL, "mpc_run_sampled: need >= 1 endpoint, num_steps >= 0");
+  if (o.n_actual != 1 && o.n_actual != num_steps)
+    return fail(I7M_EINVAL, "mpc_run_sampled: n_actual must be 1 or num_steps");
+  if (!xstart || !endpoints || !fhyp || !f_actual || !dist_out)
+    return fail(I7M_EINVAL, "mpc_run_sampled: null xstart, endpoints, fhyp, f_actual or dist_out");
+  if (G == 0) return I7M_OK;
+  HIPCHK(hipSetDevice(h->dev));
+  const int N = h->cfg.N, B = G * H;
+  const size_t T = 18 * (size_t)N - 6;
+  const bool admm = h->cfg.qp_mode == I7M_QP_ADMM;
+  // per-run state beyond the handle's buffers: per group the state, XU_best, the scored
+  // hypothesis, goal index and alive flag; the schedules and the histories
+  double *d_ep = nullptr, *d_xcur = nullptr, *d_xub = nullptr, *d_fact = nullptr, *d_noise = nullptr, *d_dist = nullptr,
+         *d_q = nullptr, *d_fb = nullptr, *d_rho0 = nullptr;
+  int *d_best = nullptr, *d_gi = nullptr, *d_alive = nullptr, *d_bh = nullptr;
+  auto cleanup = [&]() {
+    for (void* p : {(void*)d_ep, (void*)d_xcur, (void*)d_xub, (void*)d_fact, (void*)d_noise, (void*)d_dist, (void*)d_q,
+                    (void*)d_fb, (void*)d_rho0, (void*)d_best, (void*)d_gi, (void*)d_alive, (void*)d_bh})
+      if (p) (void)hipFree(p);
+  };
+  const size_t hist = (size_t)std::max(num_steps, 1) * G;
+  if (hipMalloc(&d_ep, 3 * 8 * (size_t)n_endpoints) != hipSuccess || hipMalloc(&d_xcur, 12 * 8 * (size_t)G) != hipSuccess ||
+      hipMalloc(&d_xub, 8 * T * G) != hipSuccess || hipMalloc(&d_fact, 6 * 8 * (size_t)o.n_actual * G) != hipSuccess ||
+      (noise && num_steps > 0 && hipMalloc(&d_noise, 3 * 8 * (size_t)num_steps * B) != hipSuccess) ||
+      hipMalloc(&d_dist, 8 * hist) != hipSuccess || hipMalloc(&d_q, 6 * 8 * hist) != hipSuccess ||
+      hipMalloc(&d_fb, 6 * 8 * hist) != hipSuccess || hipMalloc(&d_rho0, 8 * (size_t)B) != hipSuccess ||
+      hipMalloc(&d_best, 4 * (size_t)G) != hipSuccess || hipMalloc(&d_gi, 4 * (size_t)G) != hipSuccess ||
+      hipMalloc(&d_alive, 4 * (size_t)G) != hipSuccess || hipMalloc(&d_bh, 4 * hist) != hipSuccess) {
+    cleanup();
+    return fail(I7M_ENOMEM, "mpc_run_sampled: device allocation failed");
+  }
+  // host staging, alive until the final synchronize
+  std::vector<double> goals((size_t)B * 3 * N), xrows((size_t)B * 12), rho0((size_t)B, h->cfg.admm_rho);
+  std::vector<int> ones((size_t)G, 1);
+  auto run = [&]() -> int {
+    // src/gato_mpc_batch_sample.py:111-128: goal = endpoint 0 tiled, XU = [xstart, 0...], every
+    // row of a group at the group's start state, the hypotheses set on the solver
+    for (size_t b = 0; b < (size_t)B; ++b) {
+      for (int k = 0; k < N; ++k)
+        for (int r = 0; r < 3; ++r) goals[(b * N + k) * 3 + r] = endpoints[r];
+      for (int r = 0; r < 12; ++r) xrows[b * 12 + r] = xstart[(b / H) * 12 + r];
+    }
+    int rc2;
+    if ((rc2 = copy_in(h, h->d_xs, xrows.data(), xrows.size()))) return rc2;
+    if ((rc2 = copy_in(h, d_xcur, xstart, (size_t)G * 12))) return rc2;
+    if ((rc2 = copy_in(h, h->d_goal, goals.data(), goals.size()))) return rc2;
+    if ((rc2 = copy_in(h, d_ep, endpoints, 3 * (size_t)n_endpoints))) return rc2;
+    if ((rc2 = copy_in(h, d_fact, f_actual, 6 * (size_t)o.n_actual * G))) return rc2;
+    if (d_noise && (rc2 = copy_in(h, d_noise, noise, 3 * (size_t)num_steps * B))) return rc2;
+    if ((rc2 = copy_in(h, d_rho0, rho0.data(), rho0.size()))) return rc2;
+    HIPCHK(hipMemsetAsync(h->d_xu, 0, 8 * (size_t)B * T, h->stream));
+    HIPCHK(hipMemcpy2DAsync(h->d_xu, T * 8, xrows.data(), 12 * 8, 12 * 8, (size_t)B, hipMemcpyHostToDevice, h->stream));
+    HIPCHK(hipMemsetAsync(d_gi, 0, 4 * (size_t)G, h->stream));
+    HIPCHK(hipMemsetAsync(d_best, 0, 4 * (size_t)G, h->stream));  // the initial solve's XU_best is row 0, :128
+    HIPCHK(hipMemcpyAsync(d_alive, ones.data(), 4 * (size_t)G, hipMemcpyHostToDevice, h->stream));
+    HIPCHK(hipMemsetAsync(h->d_fext, 0, (size_t)h->cfg.max_batch * 6 * 8, h->stream));
+    if ((rc2 = copy_in(h, h->d_fext, fhyp, (size_t)B * 6))) return rc2;
+    HIPCHK(hipStreamSynchronize(h->stream));
+    h->has_fext = true;
+    h->fext_frame = o.frame;
+    drop_graphs(h);  // captured graphs hold the old wrench kernel choice
+    // i7m_admm_reset of the rows [lo, lo + n), asynchronous on stream s
+    auto admm_reset_rows = [&](long lo, int n, int what, hipStream_t s) -> int {
+      const long m = 12L * N;
+      const AdmmArgs a = admm_layout(h->d_admm, h->d_admm_it, h->cfg.max_batch, N, lo);
+      if (what & I7M_ADMM_RESET_PRIMAL) {
+        HIPCHK(hipMemsetAsync(a.sx, 0, (size_t)n * T * 8, s));
+        HIPCHK(hipMemsetAsync(a.sz, 0, (size_t)n * m * 8, s));
+        HIPCHK(hipMemsetAsync(a.sq, 0, (size_t)n * T * 8, s));
+      }
+      if (what & I7M_ADMM_RESET_DUAL) HIPCHK(hipMemsetAsync(a.sy, 0, (size_t)n * m * 8, s));
+      if (what & I7M_ADMM_RESET_RHO)
+        HIPCHK(hipMemcpyAsync(a.srho, d_rho0 + lo, (size_t)n * 8, hipMemcpyDeviceToDevice, s));
+      return I7M_OK;
+    };
+    // the rows [lo, lo + n) (whole groups) through every MPC step on stream s, as i7m_mpc_run's
+    // ranges: the groups are independent, so a staggered range runs its steps on its own
+    auto loop = [&](long lo, int n, hipStream_t s, StaggerMark* mark) -> int {
+      const long glo = lo / H;
+      const int ng = n / H;
+      double *xu = h->d_xu + lo * T, *out = h->d_out + lo * T, *xs = h->d_xs + lo * 12, *g = h->d_goal + lo * 3 * N;
+      SampledArgs a{};
+      a.N = N;
+      a.H = H;
+      a.n_endpoints = n_endpoints;
+      a.frame_world = o.frame == I7M_WRENCH_WORLD;
+      a.keep_best = o.keep_best != 0;
+      a.sim_dt = o.sim_dt;
+      a.decay = o.decay;
+      a.xs = xs;
+      a.XU = xu;
+      a.xu_new = out;
+      a.goals = g;
+      a.fext = h->d_fext + lo * 6;
+      a.xcur = d_xcur + glo * 12;
+      a.xub = d_xub + glo * T;
+      a.best = d_best + glo;
+      a.goal_idx = d_gi + glo;
+      a.alive = d_alive + glo;
+      a.endpoints = d_ep;
+      int rc3;
+      if (admm && (rc3 = admm_reset_rows(lo, n, I7M_ADMM_RESET_ALL, s))) return rc3;  // solver state afresh
+      if ((rc3 = run_sqp(h, n, xu, out, xs, g, 3, h->d_stats + lo, lo, s, mark))) return rc3;
+      // launch i: select(i - 1) (i = 0: the initial solve's row 0), then plant(i) ... goal(i);
+      // the last launch only selects
+      for (int i = 0; i <= num_steps; ++i) {
+        a.select = i == 0 ? 2 : 1;
+        a.plant = i < num_steps;
+        const size_t rec = ((size_t)std::max(i - 1, 0)) * G + glo, cur = (size_t)std::min(i, std::max(num_steps - 1, 0)) * G + glo;
+        a.noise = d_noise && i > 0 ? d_noise + ((size_t)(i - 1) * B + lo) * 3 : nullptr;
+        a.best_out = d_bh + rec;
+        a.fbest_out = d_fb + rec * 6;
+        a.f_actual = d_fact + ((size_t)(o.n_actual > 1 ? std::min(i, o.n_actual - 1) : 0) * G + glo) * 6;
+        a.dist_out = d_dist + cur;
+        a.q_out = d_q + cur * 6;
+        hipLaunchKernelGGL(k_sampled_step, dim3(ng), dim3((H + 63) / 64 * 64), 0, s, h->d_model, a);
+        HIPCHK(hipGetLastError());
+        if (!a.plant) break;
+        if (admm && o.reset_what && (rc3 = admm_reset_rows(lo, n, o.reset_what, s))) return rc3;
+        if ((rc3 = run_sqp(h, n, xu, out, xs, g, 3, h->d_stats + lo, lo, s))) return rc3;
+      }
+      return I7M_OK;
+    };
+    if (stagger_applies(h->tune, h->cfg.qp_mode, B)) {
+      if ((rc2 = run_staggered(h, B, loop, stagger_cut_grouped(B, H)))) return rc2;
+    } else if ((rc2 = loop(0, B, h->stream, nullptr))) {
+      return rc2;
+    }
+    if (num_steps > 0) {
+      if ((rc2 = copy_out(h, dist_out, d_dist, hist))) return rc2;
+      if (q_out && (rc2 = copy_out(h, q_out, d_q, hist * 6))) return rc2;
+      if (fbest_out && (rc2 = copy_out(h, fbest_out, d_fb, hist * 6))) return rc2;
+      if (best_out) HIPCHK(hipMemcpyAsync(best_out, d_bh, 4 * hist, hipMemcpyDeviceToHost, h->stream));
+    }
+    if (xcur_out && (rc2 = copy_out(h, xcur_out, d_xcur, (size_t)G * 12))) return rc2;
+    if (xu_best_out && (rc2 = copy_out(h, xu_best_out, d_xub, (size_t)G * T))) return rc2;
+    if (fhyp_out && (rc2 = copy_out(h, fhyp_out, h->d_fext, (size_t)B * 6))) return rc2;
+    HIPCHK(hipStreamSynchronize(h->stream));
+    return I7M_OK;
+  };
+  const int rc = run();
   (void)hipStreamSynchronize(h->stream);
   cleanup();
   return rc;

@@ -188,6 +188,13 @@ inline bool stagger_applies(const Tuning& t, int qp_mode, int B) {
 // problems per wave and clamped to the batch (the rounded split of a small B must not
 // run past it); an empty second range is skipped.
 inline long stagger_cut(int B) { return std::min<long>(((long)(B / 2) + 3) / 4 * 4, B); }
+// The cut of a batch whose rows come in groups of H (a power of two; i7m_mpc_run_sampled): the
+// smallest multiple of lcm(H, 4) that is >= B / 2, clamped to the batch, so that no group straddles
+// it and the first range still fills k_admm_iter's waves.
+inline long stagger_cut_grouped(int B, int H) {
+  const long L = std::max(H, 4);
+  return std::min<long>(((long)B + 2 * L - 1) / (2 * L) * L, B);
+}
 
 // How many chunks a host-to-host solve of B problems runs in.
 inline int h2h_chunks_for(const Tuning& t, int qp_mode, int B) {

@@ -1,0 +1,117 @@
+"""Drop-in for the reference's ``src/gato_mpc_batch_sample.py``: ``MPC_GATO_Batch_Sample``, the
+closed loop that estimates the external force by solving ``batch_size`` wrench hypotheses every
+control step and keeping the trajectory whose one-step prediction best matches the measured state
+(src/gato_mpc_batch_sample.py:74-300, with the controller's selection / resampling rule,
+gato_controller.py:109-129).  The whole loop runs on the device (``i7m_mpc_run_sampled``): no
+host round trip per step.
+
+What differs from the reference, on purpose:
+  * the hypotheses and the resampling noise come from ``numpy.random.default_rng(seed)``, drawn
+    up front with the reference's shapes and zeroing (torques 0, row 0 zero, :37-40,291-297); the
+    reference's global ``np.random`` draw order is not reproduced;
+  * the actual force is ``constant_f_ext`` for the whole run (zero if None), a WORLD-frame force
+    like the hypotheses; the reference random-walks it every step (:244-250) and applies it to the
+    plant as a joint-6 LOCAL force (:96-102) while it scores the hypotheses as world-frame ones;
+  * one rk4 step of ``sim_dt`` (<= dt) per control step (the reference's split at a knot boundary,
+    :170-187, never triggers then);
+  * ``resample_f_ext=True`` perturbs every row but row 0 (:291-298: keep_best = 0, decay = 1);
+    pass ``keep_best=True, decay=0.97`` for the controller's rule (gato_controller.py:120-129).
+"""
+from __future__ import annotations
+
+import time
+
+import numpy as np
+
+from . import _lib
+from .model import default_model
+
+_SIZES = (1, 2, 4, 8, 16, 32, 64, 128, 256)
+
+
+class MPC_GATO_Batch_Sample:
+    def __init__(self, model=None, N=32, dt=0.01, batch_size=4, constant_f_ext=None, resample_f_ext=False,
+                 f_ext_std=1.0, f_ext_resample_std=2.0, seed=None, qp_mode="admm", keep_best=False, decay=1.0,
+                 device_id=0):
+        if batch_size not in _SIZES:
+            raise ValueError(f"Batch size {batch_size} not supported")
+        if qp_mode not in ("direct", "admm"):
+            raise ValueError("qp_mode must be 'direct' or 'admm'")
+        self.model = model or default_model()
+        self.N, self.dt, self.batch_size = int(N), float(dt), int(batch_size)
+        self.qp_mode = _lib.QP_ADMM if qp_mode == "admm" else _lib.QP_DIRECT
+        self.device_id = device_id
+        self.resample_f_ext = bool(resample_f_ext)
+        self.f_ext_resample_std = float(f_ext_resample_std)
+        self.keep_best, self.decay = bool(keep_best), float(decay)
+        self.rng = np.random.default_rng(seed)
+        if f_ext_std != 0.0:  # src/gato_mpc_batch_sample.py:37-40
+            self.f_ext_batch = self.rng.normal(0, f_ext_std, (self.batch_size, 6))
+            self.f_ext_batch[:, 3:] = 0.0
+            self.f_ext_batch[0] = 0.0
+        else:
+            self.f_ext_batch = np.zeros((self.batch_size, 6))
+        self.actual_f_ext = np.zeros(6)
+        if constant_f_ext is not None:
+            self.actual_f_ext[:3] = np.asarray(constant_f_ext, float).reshape(-1)[:3]
+        self.xpath = []
+        self._h = None
+        self._cap = 0
+
+    def _handle(self, rows):
+        if self._h is None or self._cap < rows:
+            self._h = _lib.Handle(self.model, N=self.N, dt=self.dt, max_batch=rows, device_id=self.device_id,
+                                  qp_mode=self.qp_mode)
+            self._cap = rows
+        return self._h
+
+    def run_mpc_groups(self, xstarts, endpoints, sim_dt=0.001, sim_time=5, f_actual=None):
+        """G independent controllers, one per row of xstarts (G, 12), each with this object's
+        hypotheses and its own resampling noise.  f_actual: (6,), (G, 6) or (num_steps, G, 6)
+        world-frame wrenches (default: constant_f_ext for every group).  Returns (xpaths, stats): a
+        list of G q-paths, and the reference's stats keys with a (logged steps, G) layout, plus
+        'best_ids' and 'f_ext_best' (every step)."""
+        xs = np.asarray(xstarts, float).reshape(-1, 12)
+        G, H = xs.shape[0], self.batch_size
+        num_steps = int(sim_time / sim_dt)
+        fa = np.tile(self.actual_f_ext, (G, 1)) if f_actual is None else np.asarray(f_actual, float)
+        if fa.size == 6:
+            fa = np.tile(fa.reshape(6), (G, 1))
+        noise = None
+        if self.resample_f_ext:  # (batch_size, 6) normals per step, torques dropped, :294-296
+            noise = self.rng.normal(0, self.f_ext_resample_std, (num_steps, G * H, 6))[:, :, :3]
+        h = self._handle(G * H)
+        t0 = time.perf_counter()
+        r = h.mpc_run_sampled(xs, endpoints, num_steps, np.tile(self.f_ext_batch, (G, 1)), fa, noise=noise,
+                              sim_dt=sim_dt, frame="world", reset_what=_lib.ADMM_RESET_ALL, keep_best=self.keep_best,
+                              decay=self.decay)
+        per_step = (time.perf_counter() - t0) / max(num_steps, 1)
+        self.f_ext_batch = r["fhyp"][:H].copy()
+        ran = np.isfinite(r["q"][:, :, 0])  # a group's path ends with the step it stopped at
+        xpaths = [[q for q in r["q"][ran[:, g], g]] for g in range(G)]
+        every = max(int(round(0.05 / sim_dt)), 1)  # the reference logs every 0.05 s, :236-242
+        log = np.arange(0, num_steps, every)
+        stats = {
+            "solve_times": [round(per_step, 5)] * len(log),  # the device loop's mean time per step
+            "goal_distances": np.round(r["dist"][log], 5),
+            # the controls stay on the device between steps: only the final one is returned
+            "control_inputs": [np.round(r["xu_best"][:, 12:18], 5)],
+            "best_ids": r["best"],
+            "f_ext_best": r["fbest"],
+        }
+        self.last = r
+        return xpaths, stats
+
+    def run_mpc(self, xstart, endpoints, sim_dt=0.001, sim_time=5):
+        """One controller, as the reference's run_mpc (src/gato_mpc_batch_sample.py:106-252):
+        (xpath, stats), xpath one q per control step until the final goal is reached."""
+        xpaths, st = self.run_mpc_groups(np.asarray(xstart, float).reshape(1, 12), endpoints, sim_dt, sim_time)
+        self.xpath += xpaths[0]
+        stats = {
+            "solve_times": st["solve_times"],
+            "goal_distances": [float(d) for d in st["goal_distances"][:, 0] if np.isfinite(d)],
+            "control_inputs": [st["control_inputs"][0][0]],
+            "best_ids": st["best_ids"][:, 0],
+            "f_ext_best": st["f_ext_best"][:, 0],
+        }
+        return self.xpath, stats
