@@ -85,7 +85,10 @@ struct Timing {
 
 struct i7m_handle {
   i7m_config cfg;
+  long N = 0, T = 0;  // the horizon and the length of an XU row, 18 N - 6
   int dev = 0;
+  std::vector<void*> owned;  // every device allocation of the handle (dev_alloc); i7m_destroy frees them
+  size_t scratch = 0;        // doubles in each of d_sol / d_aux / d_out (the query hooks chunk through them)
   hipStream_t own = nullptr, stream = nullptr;
   DevModel* d_model = nullptr;
   // batch buffers (max_batch problems)
@@ -165,8 +168,8 @@ DevModel make_dev_model(const i7m_model& m) {
 
 SolveParams params_of(const i7m_handle* h, int B, int goal_stride) {
   SolveParams P;
-  P.N = h->cfg.N;
-  P.T = 18 * h->cfg.N - 6;
+  P.N = (int)h->N;
+  P.T = (int)h->T;
   P.B = B;
   P.goal_stride = goal_stride;
   P.regularize = h->cfg.regularize;
@@ -187,6 +190,16 @@ int check_batch(const i7m_handle* h, int B, int goal_stride) {
     return fail(I7M_EINVAL, "batch " + std::to_string(B) + " outside [0, max_batch=" +
                                 std::to_string(h->cfg.max_batch) + "]");
   if (goal_stride != 3 && goal_stride != 6) return fail(I7M_EINVAL, "goal_stride must be 3 or 6");
+  return I7M_OK;
+}
+
+// The opening of a batch entry point: check_batch, then for B > 0 the caller's required pointers
+// (`ptrs`: all non-null) and the device made current.  (B == 0 passes: the caller returns I7M_OK.)
+int open_batch(i7m_handle* h, int B, int goal_stride, bool ptrs, const char* null_msg = "null pointer") {
+  const int rc = check_batch(h, B, goal_stride);
+  if (rc || B == 0) return rc;
+  if (!ptrs) return fail(I7M_EINVAL, null_msg);
+  HIPCHK(hipSetDevice(h->dev));
   return I7M_OK;
 }
 
@@ -218,14 +231,30 @@ int timed(i7m_handle* h, hipStream_t s, int kid, F&& launch) {
   return I7M_OK;
 }
 
+// Every allocation of the handle: recorded on it, freed by i7m_destroy (also after a failed create).
+template <class P>
+bool dev_alloc(i7m_handle* h, P** p, size_t bytes) {
+  void* q = nullptr;
+  if (hipMalloc(&q, bytes ? bytes : 8) != hipSuccess) return false;
+  h->owned.push_back(q);
+  *p = static_cast<P*>(q);
+  return true;
+}
+
 // Per-problem work buffers of a contiguous range of problems [b0, b0 + B): every kernel indexes
-// them by its local problem index, so a range is just offset base pointers.
+// them by its local problem index, so a range is just offset base pointers (bufs_at).
 struct Bufs {
+  long b0;  // the range's first problem
   double* lin;
   double* cost;
   double* qpd;
   double* kbuf;
-  const double* fext;  // nullptr: no external wrench
+  double* sol;          // the QP's solution (T per problem)
+  int* active;
+  ProblemStats* stats;  // the handle's own stats rows (a caller of run_sqp may name others)
+  double* lsbase;       // split line search: base merits handed to the second launch
+  int* lspend;          // and the pending flags
+  const double* fext;   // nullptr: no external wrench
   // box mode only (nullptr otherwise)
   double *bx, *bzl, *bzu, *bsig, *bh, *bdxa, *bhinv, *bdh;
   IpmState* bst;
@@ -234,49 +263,55 @@ struct Bufs {
   AdmmArgs adm;
 };
 
-// per-problem sizes of the ADMM buffers (doubles), in the order admm_layout lays them out
+// The handle's ADMM allocation: an array of buffers, each (max_batch, size) row-major.  Per-problem
+// sizes, each buffer's offset and the total, in doubles.
 constexpr int ADM_NBUF = 15;
-void admm_sizes(long N, long sz[ADM_NBUF]) {
-  const long T = 18 * N - 6, m = 12 * N;
-  const long v[ADM_NBUF] = {T, m, m, T, 1,                        // x z y q rho (state)
-                            36 * N, T, m, T, m, T, m,               // Pq Pd I qs ls D E
-                            ADM_REC * N, T, 1};                     // stage records, w (h), c
-  for (int i = 0; i < ADM_NBUF; ++i) sz[i] = v[i];
-}
-// AdmmArgs pointers of problems [b0, ...) in the handle's ADMM allocation (array-of-buffers, each
-// (max_batch, size) row-major)
-AdmmArgs admm_layout(double* base, int* its, long Bm, long N, long b0) {
-  long sz[ADM_NBUF];
-  admm_sizes(N, sz);
-  double* p[ADM_NBUF];
-  double* cur = base;
+struct AdmmWalk {
+  long sz[ADM_NBUF], off[ADM_NBUF], total;
+};
+AdmmWalk admm_walk(const i7m_handle* h) {
+  const long Bm = h->cfg.max_batch, N = h->N, T = h->T, m = 12 * N;
+  AdmmWalk w{{T, m, m, T, 1,              // x z y q rho (state)
+              36 * N, T, m, T, m, T, m,   // Pq Pd I qs ls D E
+              ADM_REC * N, T, 1},         // stage records, w (h), c
+             {}, 0};
   for (int i = 0; i < ADM_NBUF; ++i) {
-    p[i] = cur + b0 * sz[i];
-    cur += (Bm * sz[i] + 1) & ~1L;  // every buffer 16-byte aligned (k_admm_iter's 16-byte loads)
+    w.off[i] = w.total;
+    w.total += (Bm * w.sz[i] + 1) & ~1L;  // every buffer 16-byte aligned (k_admm_iter's 16-byte loads)
   }
+  return w;
+}
+// AdmmArgs pointers of problems [b0, ...) in the handle's ADMM allocation
+AdmmArgs admm_layout(const i7m_handle* h, long b0) {
+  const long Bm = h->cfg.max_batch;
+  const AdmmWalk w = admm_walk(h);
+  double* p[ADM_NBUF];
+  for (int i = 0; i < ADM_NBUF; ++i) p[i] = h->d_admm + w.off[i] + b0 * w.sz[i];
   AdmmArgs a{};
   a.sx = p[0]; a.sz = p[1]; a.sy = p[2]; a.sq = p[3]; a.srho = p[4];
   a.Pq = p[5]; a.Pd = p[6]; a.I = p[7]; a.qs = p[8]; a.ls = p[9]; a.D = p[10]; a.E = p[11];
   a.R = p[12]; a.w = p[13]; a.cs = p[14];
-  a.iters = its + b0 * I7M_MAX_SQP;
-  a.status = its + (Bm + b0) * I7M_MAX_SQP;
-  a.abase = base;  // k_admm_iter reaches every array through one buffer resource over the allocation
-  a.abytes = (long)(cur - base) * 8;
+  a.iters = h->d_admm_it + b0 * I7M_MAX_SQP;
+  a.status = h->d_admm_it + (Bm + b0) * I7M_MAX_SQP;
+  a.abase = h->d_admm;  // k_admm_iter reaches every array through one buffer resource over the allocation
+  a.abytes = w.total * 8;
   return a;
-}
-size_t admm_doubles(long Bm, long N) {
-  long sz[ADM_NBUF];
-  admm_sizes(N, sz);
-  size_t t = 0;
-  for (int i = 0; i < ADM_NBUF; ++i) t += (size_t)((Bm * sz[i] + 1) & ~1L);
-  return t;
 }
 
 Bufs bufs_at(const i7m_handle* h, long b0) {
-  const long N = h->cfg.N, T = 18 * N - 6;
-  Bufs W{h->d_lin + b0 * (N - 1) * LIN_STRIDE, h->d_cost + b0 * N * COST_STRIDE,
-         h->d_qpd + b0 * (N - 1) * QPD_STRIDE, h->d_kbuf + b0 * (N - 1) * KBUF_STRIDE, h->has_fext ? h->d_fext + 6 * b0 : nullptr,
-         nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+  const long N = h->N, T = h->T;
+  Bufs W{};
+  W.b0 = b0;
+  W.lin = h->d_lin + b0 * (N - 1) * LIN_STRIDE;
+  W.cost = h->d_cost + b0 * N * COST_STRIDE;
+  W.qpd = h->d_qpd + b0 * (N - 1) * QPD_STRIDE;
+  W.kbuf = h->d_kbuf + b0 * (N - 1) * KBUF_STRIDE;
+  W.sol = h->d_sol + b0 * T;
+  W.active = h->d_active + b0;
+  W.stats = h->d_stats + b0;
+  W.lsbase = h->d_lsbase + b0;
+  W.lspend = h->d_lspend + b0;
+  W.fext = h->has_fext ? h->d_fext + 6 * b0 : nullptr;
   if (h->cfg.qp_mode == I7M_QP_BOX) {
     W.bx = h->d_bx + b0 * T;
     W.bzl = h->d_bzl + b0 * T;
@@ -289,7 +324,7 @@ Bufs bufs_at(const i7m_handle* h, long b0) {
     W.bst = h->d_bst + b0;
     W.bact = h->d_bact + b0;
   }
-  if (h->cfg.qp_mode == I7M_QP_ADMM) W.adm = admm_layout(h->d_admm, h->d_admm_it, h->cfg.max_batch, N, b0);
+  if (h->cfg.qp_mode == I7M_QP_ADMM) W.adm = admm_layout(h, b0);
   return W;
 }
 
@@ -409,10 +444,8 @@ int launch_linesearch(i7m_handle* h, hipStream_t s, const Bufs& W, const SolvePa
     // for the problems that have not accepted a candidate
     const int R = P.N >= 64 ? 1 : 64 / P.N;
     const int c_split = 1 + R * h->tune.ls_tail;
-    const long b0 = W.lin - h->d_lin;  // this range's first problem (bufs_at offsets lin by b0 (N-1) stride)
-    const long pb = b0 / ((long)(P.N - 1) * LIN_STRIDE);
-    const LsSplit first{0, c_split, h->d_lsbase + pb, h->d_lspend + pb};
-    const LsSplit second{c_split, 1 + NALPHA, h->d_lsbase + pb, h->d_lspend + pb};
+    const LsSplit first{0, c_split, W.lsbase, W.lspend};
+    const LsSplit second{c_split, 1 + NALPHA, W.lsbase, W.lspend};
     int rc = timed(h, s, I7M_K_LINESEARCH, [&](hipEvent_t ea, hipEvent_t eb) {
       hipExtLaunchKernelGGL(ls_kernel(h->spec, fw, 1), dim3(P.B), dim3(64), lds, s, ea, eb, 0, h->d_model, P, xu, xu_out, sol,
                             goals, W.fext, active, st, alpha_out, iter, mode, W.lin, W.cost, first);
@@ -529,12 +562,10 @@ int solve_qp(i7m_handle* h, hipStream_t s, const Bufs& W, const SolveParams& P, 
   const BoxParams BP = box_params(h);
   const dim3 g(P.B), blk(64);
   if (h->tune.ipm_mode != 2) {
+    IpmFusedArgs fa{h->d_model, P, BP, xu, xs, W.lin, W.cost, W.qpd, active, W.kbuf, sol, sol,
+                    W.bx, W.bzl, W.bzu, W.bsig, W.bh, W.bdxa, W.bst, W.bact, W.bhinv, W.bdh};
 #ifdef I7M_DIAG
-    const IpmFusedArgs fa{h->d_model, P, BP, xu, xs, W.lin, W.cost, W.qpd, active, W.kbuf, sol, sol,
-                          W.bx, W.bzl, W.bzu, W.bsig, W.bh, W.bdxa, W.bst, W.bact, W.bhinv, W.bdh, h->ablate};
-#else
-    const IpmFusedArgs fa{h->d_model, P, BP, xu, xs, W.lin, W.cost, W.qpd, active, W.kbuf, sol, sol,
-                          W.bx, W.bzl, W.bzu, W.bsig, W.bh, W.bdxa, W.bst, W.bact, W.bhinv, W.bdh};
+    fa.ablate = h->ablate;
 #endif
     rc = timed(h, s, I7M_K_IPM_FUSED, [&](hipEvent_t ea, hipEvent_t eb) {
       if (h->tune.ipm_mode == 0)
@@ -574,7 +605,7 @@ int solve_qp(i7m_handle* h, hipStream_t s, const Bufs& W, const SolveParams& P, 
 }
 
 int launch_fused(i7m_handle* h, hipStream_t s, const Bufs& W, const SolveParams& P, const double* xu_in, double* xu_out,
-                 const double* xs, const double* goals, ProblemStats* st, long b0) {
+                 const double* xs, const double* goals, ProblemStats* st) {
   const int nw = fused_waves(h->tune, P.B);
   // I7M_PIPE_FUSED_ITER: one launch per SQP iteration, else one per solve
   const int launches = h->tune.pipeline == I7M_PIPE_FUSED_ITER ? h->cfg.max_sqp_iters : 1;
@@ -583,7 +614,7 @@ int launch_fused(i7m_handle* h, hipStream_t s, const Bufs& W, const SolveParams&
     const int rc = timed(h, s, I7M_K_SQP_FUSED, [&](hipEvent_t ea, hipEvent_t eb) {
       e = i7m_launch_sqp_fused(h->spec, nw, h->fext_frame == I7M_WRENCH_WORLD, launches > 1 ? i : -1, s, ea, eb, h->d_model,
                                &P, i == 0 ? xu_in : xu_out, xu_out, xs, goals, W.fext, W.lin, W.cost, W.qpd, W.kbuf,
-                               h->d_sol + b0 * P.T, h->d_active + b0, st);
+                               W.sol, W.active, st);
     });
     if (rc) return rc;
     if (e != hipSuccess) return fail(I7M_EHIP, std::string("k_sqp_fused launch: ") + hipGetErrorString(e));
@@ -598,15 +629,17 @@ int launch_fused(i7m_handle* h, hipStream_t s, const Bufs& W, const SolveParams&
 // stream s (h->stream unless the host-to-host path splits the batch into chunks).
 // (Splitting a device-resident batch into ranges on several streams, so that waves of different
 // kernels share a SIMD, was measured at 2-4 ranges and gave nothing: DESIGN.md §7.)
+// d_st: where the stats go; nullptr = the handle's own rows of these problems.
 // mark: the staggered ranges' mark, recorded in this solve's first QP (ADMM mode; StaggerMark).
 int run_sqp(i7m_handle* h, int B, const double* d_xu_in, double* d_xu, const double* d_xs, const double* d_goals,
             int goal_stride, ProblemStats* d_st, long b0 = 0, hipStream_t s = nullptr, StaggerMark* mark = nullptr) {
   const Bufs W = bufs_at(h, b0);
   const SolveParams P = params_of(h, B, goal_stride);
   if (!s) s = h->stream;
-  int* act = h->d_active + b0;
-  double* qbuf = h->d_sol + b0 * P.T;
-  if (use_fused(h->tune, h->cfg.qp_mode)) return launch_fused(h, s, W, P, d_xu_in, d_xu, d_xs, d_goals, d_st, b0);
+  if (!d_st) d_st = W.stats;
+  int* act = W.active;
+  double* qbuf = W.sol;
+  if (use_fused(h->tune, h->cfg.qp_mode)) return launch_fused(h, s, W, P, d_xu_in, d_xu, d_xs, d_goals, d_st);
   if (h->cfg.qp_mode == I7M_QP_ADMM && B > 0) {
     // this solve's OSQP records start at -1 ("no QP"): a problem that stops after SQP iteration
     // 0 must not report an earlier call's counts for the iterations it did not run
@@ -688,16 +721,39 @@ int copy_out(i7m_handle* h, double* dst, const double* src, size_t n, hipStream_
   return I7M_OK;
 }
 
+// The inputs of problems [lo, lo + n) from the caller's host arrays (whole-batch pointers) into the
+// handle's d_xu / d_xs / d_goal rows, on stream s (nullptr: the handle's).  xcur may be null.
+int stage_in(i7m_handle* h, long lo, long n, const double* xu, const double* xcur, const double* goals, int goal_stride,
+             hipStream_t s = nullptr) {
+  const size_t T = h->T, G = (size_t)h->N * goal_stride;
+  int rc;
+  if ((rc = copy_in(h, h->d_xu + lo * T, xu + lo * T, n * T, s))) return rc;
+  if (xcur && (rc = copy_in(h, h->d_xs + lo * 12, xcur + lo * 12, (size_t)n * 12, s))) return rc;
+  return copy_in(h, h->d_goal + lo * G, goals + lo * G, n * G, s);
+}
+// The results of problems [lo, lo + n): d_xu's rows, and their stats if the caller asked for them.
+int stage_out(i7m_handle* h, long lo, long n, double* xu_out, i7m_problem_stats* stats, hipStream_t s = nullptr) {
+  const size_t T = h->T;
+  if (!s) s = h->stream;
+  const int rc = copy_out(h, xu_out + lo * T, h->d_xu + lo * T, n * T, s);
+  if (rc) return rc;
+  if (stats && n > 0)
+    HIPCHK(hipMemcpyAsync(stats + lo, h->d_stats + lo, sizeof(ProblemStats) * (size_t)n, hipMemcpyDeviceToHost, s));
+  return I7M_OK;
+}
+// run_sqp in place on the staged rows [lo, lo + n)
+int solve_staged(i7m_handle* h, long lo, long n, int goal_stride, hipStream_t s, StaggerMark* mark = nullptr) {
+  double* dxu = h->d_xu + lo * h->T;
+  return run_sqp(h, (int)n, dxu, dxu, h->d_xs + lo * 12, h->d_goal + lo * h->N * goal_stride, goal_stride, nullptr, lo, s,
+                 mark);
+}
+
 // Host-to-host solve in `nch` contiguous chunks of the batch, alternating over two streams: each
 // chunk is H2D of its rows -> its SQP -> D2H of its rows and stats, so chunk i's solve runs while
 // chunk i+1 is copied in and chunk i-1 copied out (PCIe is full duplex), instead of copy-in,
 // solve, copy-out back to back.  Ordered after earlier work on h->stream; synchronous.
-int solve_h2h_pipelined(i7m_handle* h, int B, const double* xu_in, const double* xcur, const double* goals,
-                        int goal_stride, double* xu_out, i7m_problem_stats* stats, int nch);
-
-int solve_h2h_chunked_body(i7m_handle* h, int B, const double* xu_in, const double* xcur, const double* goals,
-                           int goal_stride, double* xu_out, i7m_problem_stats* stats, int nch) {
-  const size_t T = 18 * (size_t)h->cfg.N - 6, N = h->cfg.N;
+int solve_h2h_alternating(i7m_handle* h, int B, const double* xu_in, const double* xcur, const double* goals,
+                          int goal_stride, double* xu_out, i7m_problem_stats* stats, int nch) {
   int rc;
   HIPCHK(hipEventRecord(h->ev_order, h->stream));
   for (int c = 0; c < 2; ++c) HIPCHK(hipStreamWaitEvent(h->cs[c], h->ev_order, 0));
@@ -706,23 +762,15 @@ int solve_h2h_chunked_body(i7m_handle* h, int B, const double* xu_in, const doub
     const int n = (int)(hi - lo);
     if (n == 0) continue;
     hipStream_t s = h->cs[i & 1];
-    double* dxu = h->d_xu + lo * T;
-    double* dxs = h->d_xs + lo * 12;
-    double* dg = h->d_goal + lo * N * goal_stride;
-    if ((rc = copy_in(h, dxu, xu_in + lo * T, n * T, s))) return rc;
-    if ((rc = copy_in(h, dxs, xcur + lo * 12, (size_t)n * 12, s))) return rc;
-    if ((rc = copy_in(h, dg, goals + lo * N * goal_stride, n * N * goal_stride, s))) return rc;
-    if ((rc = run_sqp(h, n, dxu, dxu, dxs, dg, goal_stride, h->d_stats + lo, lo, s))) return rc;
-    if ((rc = copy_out(h, xu_out + lo * T, dxu, n * T, s))) return rc;
-    if (stats)
-      HIPCHK(hipMemcpyAsync(stats + lo, h->d_stats + lo, sizeof(ProblemStats) * (size_t)n, hipMemcpyDeviceToHost, s));
+    if ((rc = stage_in(h, lo, n, xu_in, xcur, goals, goal_stride, s)) || (rc = solve_staged(h, lo, n, goal_stride, s)) ||
+        (rc = stage_out(h, lo, n, xu_out, stats, s)))
+      return rc;
   }
   for (int c = 0; c < 2; ++c) {
     HIPCHK(hipEventRecord(h->ev_done[c], h->cs[c]));
     HIPCHK(hipStreamWaitEvent(h->stream, h->ev_done[c], 0));
   }
-  HIPCHK(hipStreamSynchronize(h->stream));
-  return I7M_OK;
+  return i7m_synchronize(h);
 }
 
 // The chunks as a three-stage pipeline: copies in on cs[0], the solves on the handle's stream
@@ -734,9 +782,8 @@ int solve_h2h_chunked_body(i7m_handle* h, int B, const double* xu_in, const doub
 // i in, and chunk i-1 out, while the device solves the chunk before.  The alternating two-stream
 // layout above issued all copy-ins at once: they shared the link and finished together, then the
 // solves ran, then the copy-outs — no overlap.
-int solve_h2h_pipelined_body(i7m_handle* h, int B, const double* xu_in, const double* xcur, const double* goals,
-                             int goal_stride, double* xu_out, i7m_problem_stats* stats, int nch) {
-  const size_t T = 18 * (size_t)h->cfg.N - 6, N = h->cfg.N;
+int solve_h2h_pipelined(i7m_handle* h, int B, const double* xu_in, const double* xcur, const double* goals,
+                        int goal_stride, double* xu_out, i7m_problem_stats* stats, int nch) {
   while ((int)h->ev_in.size() < nch) {
     hipEvent_t a = nullptr, b = nullptr;
     HIPCHK(hipEventCreateWithFlags(&a, hipEventDisableTiming));
@@ -757,11 +804,8 @@ int solve_h2h_pipelined_body(i7m_handle* h, int B, const double* xu_in, const do
   // (each stage keeps its status in a local: with h2h_pipe 3 out() runs on another thread)
   auto in = [&](int i) -> int {
     const long lo = lo_of(i), n = lo_of(i + 1) - lo;
-    int r;
-    if ((r = copy_in(h, h->d_xu + lo * T, xu_in + lo * T, n * T, h->cs[0]))) return r;
-    if ((r = copy_in(h, h->d_xs + lo * 12, xcur + lo * 12, (size_t)n * 12, h->cs[0]))) return r;
-    if ((r = copy_in(h, h->d_goal + lo * N * goal_stride, goals + lo * N * goal_stride, n * N * goal_stride, h->cs[0])))
-      return r;
+    const int r = stage_in(h, lo, n, xu_in, xcur, goals, goal_stride, h->cs[0]);
+    if (r) return r;
     HIPCHK(hipEventRecord(h->ev_in[i], h->cs[0]));
     return I7M_OK;
   };
@@ -774,10 +818,7 @@ int solve_h2h_pipelined_body(i7m_handle* h, int B, const double* xu_in, const do
     const hipStream_t ss = sstream(i);
     HIPCHK(hipStreamWaitEvent(ss, h->ev_in[i], 0));
     if (i == 1 && mark.recorded) HIPCHK(hipStreamWaitEvent(ss, mark.ev, 0));
-    double* dxu = h->d_xu + lo * T;
-    const int r = n > 0 ? run_sqp(h, (int)n, dxu, dxu, h->d_xs + lo * 12, h->d_goal + lo * N * goal_stride, goal_stride,
-                                  h->d_stats + lo, lo, ss, stag && i == 0 ? &mark : nullptr)
-                        : I7M_OK;
+    const int r = n > 0 ? solve_staged(h, lo, n, goal_stride, ss, stag && i == 0 ? &mark : nullptr) : I7M_OK;
     if (r) return r;
     HIPCHK(hipEventRecord(h->ev_cmp[i], ss));
     return I7M_OK;
@@ -785,12 +826,7 @@ int solve_h2h_pipelined_body(i7m_handle* h, int B, const double* xu_in, const do
   auto out = [&](int i) -> int {
     const long lo = lo_of(i), n = lo_of(i + 1) - lo;
     HIPCHK(hipStreamWaitEvent(h->cs[1], h->ev_cmp[i], 0));
-    int r;
-    if ((r = copy_out(h, xu_out + lo * T, h->d_xu + lo * T, n * T, h->cs[1]))) return r;
-    if (stats && n > 0)
-      HIPCHK(hipMemcpyAsync(stats + lo, h->d_stats + lo, sizeof(ProblemStats) * (size_t)n, hipMemcpyDeviceToHost,
-                            h->cs[1]));
-    return I7M_OK;
+    return stage_out(h, lo, n, xu_out, stats, h->cs[1]);
   };
   if (h->tune.h2h_pipe == 3) {
     // copies out on a second host thread: a pageable copy blocks the thread that issues it, so
@@ -837,8 +873,7 @@ int solve_h2h_pipelined_body(i7m_handle* h, int B, const double* xu_in, const do
   }
   HIPCHK(hipEventRecord(h->ev_done[1], h->cs[1]));
   HIPCHK(hipStreamWaitEvent(h->stream, h->ev_done[1], 0));
-  HIPCHK(hipStreamSynchronize(h->stream));
-  return I7M_OK;
+  return i7m_synchronize(h);
 }
 
 // Error exit of a chunked call: chunks already queued on cs[0], cs[1] and cs2 keep
@@ -855,14 +890,158 @@ int drain_after_error(i7m_handle* h, int rc) {
   g_err = msg;
   return rc;
 }
-int solve_h2h_pipelined(i7m_handle* h, int B, const double* xu_in, const double* xcur, const double* goals,
-                        int goal_stride, double* xu_out, i7m_problem_stats* stats, int nch) {
-  return drain_after_error(h, solve_h2h_pipelined_body(h, B, xu_in, xcur, goals, goal_stride, xu_out, stats, nch));
-}
 int solve_h2h_chunked(i7m_handle* h, int B, const double* xu_in, const double* xcur, const double* goals, int goal_stride,
                       double* xu_out, i7m_problem_stats* stats, int nch) {
-  if (h->tune.h2h_pipe) return solve_h2h_pipelined(h, B, xu_in, xcur, goals, goal_stride, xu_out, stats, nch);
-  return drain_after_error(h, solve_h2h_chunked_body(h, B, xu_in, xcur, goals, goal_stride, xu_out, stats, nch));
+  const auto body = h->tune.h2h_pipe ? solve_h2h_pipelined : solve_h2h_alternating;
+  return drain_after_error(h, body(h, B, xu_in, xcur, goals, goal_stride, xu_out, stats, nch));
+}
+
+// body(lo, n, stream, mark) enqueues the work of problems [lo, lo + n).  Where the batch staggers
+// (stagger_applies) it runs as two contiguous ranges on cs[0] and cs[1], the second started when
+// the first has passed its mark (the first run_sqp of `body` records it; StaggerMark), both forked
+// from and joined back into h->stream; otherwise the whole batch runs on h->stream.  Results are
+// the one-range run's: the problems are independent.
+// cut: where the second range begins; -1 = stagger_cut(B) (a caller whose problems come in groups
+// passes a cut that splits none).
+template <class Body>
+int run_ranges(i7m_handle* h, int B, Body&& body, long cut = -1) {
+  if (!stagger_applies(h->tune, h->cfg.qp_mode, B)) return body(0L, B, h->stream, (StaggerMark*)nullptr);
+  const long cuts[3] = {0, cut < 0 ? stagger_cut(B) : cut, B};
+  StaggerMark mark{h->ev_rmark, h->tune.admm_stagger, false};
+  HIPCHK(hipEventRecord(h->ev_order, h->stream));
+  for (int r = 0; r < 2; ++r) {
+    const long lo = cuts[r], hi = cuts[r + 1];
+    HIPCHK(hipStreamWaitEvent(h->cs[r], h->ev_order, 0));
+    if (hi <= lo) continue;
+    if (r == 1 && mark.recorded) HIPCHK(hipStreamWaitEvent(h->cs[1], mark.ev, 0));
+    const int rc = body(lo, (int)(hi - lo), h->cs[r], r == 0 ? &mark : nullptr);
+    if (rc) {
+      // join the ranges already started back into h->stream before the error returns (ADVICE r5):
+      // a caller that synchronises h->stream and then releases memory (Workspace) must not race them
+      const std::string msg = g_err;
+      for (int q = 0; q <= r; ++q) {
+        (void)hipEventRecord(h->ev_done[q], h->cs[q]);
+        (void)hipStreamWaitEvent(h->stream, h->ev_done[q], 0);
+      }
+      g_err = msg;
+      return rc;
+    }
+  }
+  for (int r = 0; r < 2; ++r) {
+    HIPCHK(hipEventRecord(h->ev_done[r], h->cs[r]));
+    HIPCHK(hipStreamWaitEvent(h->stream, h->ev_done[r], 0));
+  }
+  return I7M_OK;
+}
+
+// The checks every ADMM state accessor starts with; on I7M_OK with B > 0 the device is current and
+// *a is the layout from problem 0.  (B == 0 passes: the caller returns I7M_OK without work.)
+int admm_rows(i7m_handle* h, int B, AdmmArgs* a) {
+  if (!h) return fail(I7M_EINVAL, "null handle");
+  if (h->cfg.qp_mode != I7M_QP_ADMM) return fail(I7M_EINVAL, "handle is not in I7M_QP_ADMM mode");
+  if (B < 0 || B > h->cfg.max_batch) return fail(I7M_EINVAL, "batch outside [0, max_batch]");
+  if (B == 0) return I7M_OK;
+  HIPCHK(hipSetDevice(h->dev));
+  *a = admm_layout(h, 0);
+  return I7M_OK;
+}
+
+// The OSQP state of problems [lo, lo + n) afresh (what: I7M_ADMM_RESET_* bits), asynchronous on
+// stream s.  rho: n values for these rows, copied as `kind` (from the host, or device to device).
+int admm_reset_rows(i7m_handle* h, long lo, long n, int what, hipStream_t s, const double* rho, hipMemcpyKind kind) {
+  const size_t T = h->T, m = 12 * (size_t)h->N;
+  const AdmmArgs a = admm_layout(h, lo);
+  if (what & I7M_ADMM_RESET_PRIMAL) {
+    HIPCHK(hipMemsetAsync(a.sx, 0, n * T * 8, s));
+    HIPCHK(hipMemsetAsync(a.sz, 0, n * m * 8, s));
+    HIPCHK(hipMemsetAsync(a.sq, 0, n * T * 8, s));
+  }
+  if (what & I7M_ADMM_RESET_DUAL) HIPCHK(hipMemsetAsync(a.sy, 0, n * m * 8, s));
+  if (what & I7M_ADMM_RESET_RHO) HIPCHK(hipMemcpyAsync(a.srho, rho, (size_t)n * 8, kind, s));
+  return I7M_OK;
+}
+
+// One closed-loop call's device memory beyond the handle's: one allocation carved into 256-byte
+// aligned sub-buffers (carve, i7m_plan.h).  The destructor synchronises the handle's stream before
+// it frees, so on every return, error or not, nothing queued still uses the memory.
+struct Workspace {
+  i7m_handle* h;
+  char* base = nullptr;  // null: the allocation failed
+  std::vector<size_t> off;
+  template <size_t NB>
+  Workspace(i7m_handle* hh, const size_t (&bytes)[NB]) : h(hh), off(NB) {
+    const size_t total = carve(bytes, (int)NB, off.data());
+    if (hipMalloc((void**)&base, total ? total : WS_ALIGN) != hipSuccess) base = nullptr;
+  }
+  Workspace(const Workspace&) = delete;
+  ~Workspace() {
+    (void)hipStreamSynchronize(h->stream);
+    if (base) (void)hipFree(base);
+  }
+  template <class P> P* at(int i) const { return reinterpret_cast<P*>(base + off[i]); }
+};
+
+// The start of a closed loop on the handle's stream (src/osqp_mpc.py:14-27,
+// src/gato_mpc_batch_sample.py:111-128): every row's goal = endpoint 0 at every knot, XU = 0, the
+// endpoints on the device, and per instance goal index 0 and alive.  The host staging is the
+// LoopStart, which the caller keeps until its final synchronize.
+struct LoopStart {
+  size_t rows;
+  std::vector<double> goals;
+  std::vector<int> ones;
+  LoopStart(const i7m_handle* h, size_t rows_, size_t instances, const double* endpoints)
+      : rows(rows_), goals(rows_ * 3 * h->N), ones(instances, 1) {
+    for (size_t k = 0; k < goals.size(); ++k) goals[k] = endpoints[k % 3];
+  }
+};
+int loop_start(i7m_handle* h, const LoopStart& st, const double* endpoints, int n_endpoints, double* d_ep, int* d_gi,
+               int* d_alive) {
+  int rc;
+  if ((rc = copy_in(h, h->d_goal, st.goals.data(), st.goals.size()))) return rc;
+  if ((rc = copy_in(h, d_ep, endpoints, 3 * (size_t)n_endpoints))) return rc;
+  HIPCHK(hipMemsetAsync(d_gi, 0, 4 * st.ones.size(), h->stream));
+  HIPCHK(hipMemcpyAsync(d_alive, st.ones.data(), 4 * st.ones.size(), hipMemcpyHostToDevice, h->stream));
+  HIPCHK(hipMemsetAsync(h->d_xu, 0, 8 * st.rows * h->T, h->stream));
+  return I7M_OK;
+}
+
+// The query hooks' chunk loop: Bq queries, at most scratch / per_query a chunk.  Chunk rows of the
+// inputs (w doubles per query each; a null host pointer keeps its slot and copies nothing) go to
+// consecutive slots of d_aux, launch(n, in, out) runs, and the outputs come back from consecutive
+// slots of d_sol, or from `dev` where an output names a buffer of its own.
+struct QueryIn { const double* host; int w; };
+struct QueryOut { double* host; int w; double* dev = nullptr; };
+template <class Launch>
+int query_chunks(i7m_handle* h, int Bq, int per_query, std::initializer_list<QueryIn> ins,
+                 std::initializer_list<QueryOut> outs, Launch&& launch) {
+  HIPCHK(hipSetDevice(h->dev));
+  const size_t cap = h->scratch / per_query;
+  int rc;
+  for (size_t o = 0; o < (size_t)Bq; o += cap) {
+    const size_t n = std::min(cap, (size_t)Bq - o);
+    double *in[4], *out[4];
+    size_t at = 0, k = 0;
+    for (const QueryIn& q : ins) {
+      in[k] = h->d_aux + at * n;
+      if (q.host && (rc = copy_in(h, in[k], q.host + q.w * o, q.w * n))) return rc;
+      at += q.w;
+      ++k;
+    }
+    at = k = 0;
+    for (const QueryOut& q : outs) {
+      out[k++] = q.dev ? q.dev : h->d_sol + at * n;
+      if (!q.dev) at += q.w;
+    }
+    launch((int)n, in, out);
+    HIPCHK(hipGetLastError());
+    k = 0;
+    for (const QueryOut& q : outs) {
+      if (q.host && (rc = copy_out(h, q.host + q.w * o, out[k], q.w * n))) return rc;
+      ++k;
+    }
+    HIPCHK(hipStreamSynchronize(h->stream));
+  }
+  return I7M_OK;
 }
 
 }  // namespace
@@ -1007,34 +1186,44 @@ int i7m_create(const i7m_config* cfg, i7m_handle** out) {
     const hipError_t ef = i7m_prepare_sqp_fused(h->dev, cfg->N);
     if (ef != hipSuccess) return bail(fail(I7M_EHIP, std::string("k_sqp_fused LDS limit: ") + hipGetErrorString(ef)));
   }
-  const size_t Bm = (size_t)cfg->max_batch, N = (size_t)cfg->N, T = 18 * N - 6;
+  h->N = cfg->N;
+  h->T = 18 * h->N - 6;
+  const size_t Bm = (size_t)cfg->max_batch, N = (size_t)h->N, T = (size_t)h->T;
   // scratch for the query hooks: >= 114 doubles for each of >= 256 queries
-  const size_t scratch = std::max(Bm * T, (size_t)256 * 114);
-  auto alloc = [&](void** p, size_t bytes) -> bool { return hipMalloc(p, bytes ? bytes : 8) == hipSuccess; };
-  bool ok = alloc((void**)&h->d_model, sizeof(DevModel)) && alloc((void**)&h->d_xu, Bm * T * 8) &&
-            alloc((void**)&h->d_xs, Bm * 12 * 8) && alloc((void**)&h->d_goal, Bm * N * 6 * 8) &&
-            alloc((void**)&h->d_sol, scratch * 8) && alloc((void**)&h->d_lin, Bm * (N - 1) * LIN_STRIDE * 8) &&
-            alloc((void**)&h->d_cost, Bm * N * COST_STRIDE * 8) &&
-            alloc((void**)&h->d_kbuf, Bm * (N - 1) * KBUF_STRIDE * 8) && alloc((void**)&h->d_aux, scratch * 8) &&
-            alloc((void**)&h->d_qpd, Bm * (N - 1) * QPD_STRIDE * 8) &&
-            alloc((void**)&h->d_out, scratch * 8) &&
-            alloc((void**)&h->d_active, Bm * sizeof(int)) && alloc((void**)&h->d_stats, Bm * sizeof(ProblemStats)) &&
-            alloc((void**)&h->d_fext, Bm * 6 * 8) && alloc((void**)&h->d_lsbase, Bm * 8) &&
-            alloc((void**)&h->d_lspend, Bm * sizeof(int));
-  if (ok && cfg->qp_mode == I7M_QP_BOX)
-    ok = alloc((void**)&h->d_bx, Bm * T * 8) && alloc((void**)&h->d_bzl, Bm * T * 8) &&
-         alloc((void**)&h->d_bzu, Bm * T * 8) && alloc((void**)&h->d_bsig, Bm * T * 8) &&
-         alloc((void**)&h->d_bh, Bm * T * 8) && alloc((void**)&h->d_bdxa, Bm * T * 8) &&
-         alloc((void**)&h->d_bhinv, Bm * (N - 1) * 36 * 8) && alloc((void**)&h->d_bdh, Bm * T * 8) &&
-         alloc((void**)&h->d_bst, Bm * sizeof(IpmState)) && alloc((void**)&h->d_bact, Bm * sizeof(int));
+  h->scratch = std::max(Bm * T, (size_t)256 * 114);
+  bool ok = true;
+  auto need = [&](auto** p, size_t bytes) { ok = ok && dev_alloc(h, p, bytes); };
+  need(&h->d_model, sizeof(DevModel));
+  need(&h->d_xu, Bm * T * 8);
+  need(&h->d_xs, Bm * 12 * 8);
+  need(&h->d_goal, Bm * N * 6 * 8);
+  need(&h->d_sol, h->scratch * 8);
+  need(&h->d_lin, Bm * (N - 1) * LIN_STRIDE * 8);
+  need(&h->d_cost, Bm * N * COST_STRIDE * 8);
+  need(&h->d_kbuf, Bm * (N - 1) * KBUF_STRIDE * 8);
+  need(&h->d_aux, h->scratch * 8);
+  need(&h->d_qpd, Bm * (N - 1) * QPD_STRIDE * 8);
+  need(&h->d_out, h->scratch * 8);
+  need(&h->d_active, Bm * sizeof(int));
+  need(&h->d_stats, Bm * sizeof(ProblemStats));
+  need(&h->d_fext, Bm * 6 * 8);
+  need(&h->d_lsbase, Bm * 8);
+  need(&h->d_lspend, Bm * sizeof(int));
+  if (cfg->qp_mode == I7M_QP_BOX) {
+    for (double** p : {&h->d_bx, &h->d_bzl, &h->d_bzu, &h->d_bsig, &h->d_bh, &h->d_bdxa}) need(p, Bm * T * 8);
+    need(&h->d_bhinv, Bm * (N - 1) * 36 * 8);
+    need(&h->d_bdh, Bm * T * 8);
+    need(&h->d_bst, Bm * sizeof(IpmState));
+    need(&h->d_bact, Bm * sizeof(int));
+  }
   if (ok && cfg->qp_mode == I7M_QP_ADMM) {
     // k_admm_iter addresses the allocation with 32-bit byte offsets below its 0x7ff00000 marker
-    if (admm_doubles((long)Bm, (long)N) * 8 >= 0x7ff00000ull)
+    const size_t admm_bytes = (size_t)admm_walk(h).total * 8;
+    if (admm_bytes >= 0x7ff00000ull)
       return bail(fail(I7M_EINVAL, "ADMM mode: max_batch=" + std::to_string(cfg->max_batch) + " at N=" + std::to_string(N) +
                                        " needs over 2 GiB of ADMM state; use a smaller max_batch per handle"));
-    ok = alloc((void**)&h->d_admm, admm_doubles((long)Bm, (long)N) * 8) &&
-         alloc((void**)&h->d_admm_it, 2 * Bm * I7M_MAX_SQP * sizeof(int));
-    h->cfg.qp_mode = I7M_QP_ADMM;
+    need(&h->d_admm, admm_bytes);
+    need(&h->d_admm_it, 2 * Bm * I7M_MAX_SQP * sizeof(int));
     if (ok && i7m_admm_reset(h, cfg->max_batch, I7M_ADMM_RESET_ALL) != I7M_OK) ok = false;
   }
   if (!ok) return bail(fail(I7M_ENOMEM, "hipMalloc failed for max_batch=" + std::to_string(cfg->max_batch)));
@@ -1051,12 +1240,7 @@ void i7m_destroy(i7m_handle* h) {
   if (!h) return;
   (void)hipSetDevice(h->dev);
   if (h->stream) (void)hipStreamSynchronize(h->stream);
-  void* bufs[] = {h->d_model, h->d_xu, h->d_xs, h->d_goal, h->d_sol, h->d_lin, h->d_cost,
-                  h->d_kbuf, h->d_aux, h->d_out, h->d_active, h->d_stats, h->d_fext, h->d_qpd, h->d_lsbase, h->d_lspend,
-                  h->d_bx, h->d_bzl, h->d_bzu, h->d_bsig, h->d_bh, h->d_bdxa, h->d_bst, h->d_bact,
-                  h->d_bhinv, h->d_bdh, h->d_admm, h->d_admm_it};
-  for (void* p : bufs)
-    if (p) (void)hipFree(p);
+  for (void* p : h->owned) (void)hipFree(p);
   for (auto& t : h->ev) {
     (void)hipEventDestroy(t.a);
     (void)hipEventDestroy(t.b);
@@ -1122,65 +1306,43 @@ int i7m_reset(i7m_handle* h) {
 }
 
 int i7m_admm_reset(i7m_handle* h, int32_t B, int32_t what) {
-  if (!h) return fail(I7M_EINVAL, "null handle");
-  if (h->cfg.qp_mode != I7M_QP_ADMM) return fail(I7M_EINVAL, "handle is not in I7M_QP_ADMM mode");
-  if (B < 0 || B > h->cfg.max_batch) return fail(I7M_EINVAL, "batch outside [0, max_batch]");
+  AdmmArgs a{};
+  int rc = admm_rows(h, B, &a);
+  if (rc) return rc;
   if (what & ~I7M_ADMM_RESET_ALL) return fail(I7M_EINVAL, "unknown I7M_ADMM_RESET_* bits");
   if (B == 0) return I7M_OK;
-  HIPCHK(hipSetDevice(h->dev));
-  const long N = h->cfg.N, T = 18 * N - 6, m = 12 * N;
-  const AdmmArgs a = admm_layout(h->d_admm, h->d_admm_it, h->cfg.max_batch, N, 0);
-  if (what & I7M_ADMM_RESET_PRIMAL) {
-    HIPCHK(hipMemsetAsync(a.sx, 0, (size_t)B * T * 8, h->stream));
-    HIPCHK(hipMemsetAsync(a.sz, 0, (size_t)B * m * 8, h->stream));
-    HIPCHK(hipMemsetAsync(a.sq, 0, (size_t)B * T * 8, h->stream));
-  }
-  if (what & I7M_ADMM_RESET_DUAL) HIPCHK(hipMemsetAsync(a.sy, 0, (size_t)B * m * 8, h->stream));
-  if (what & I7M_ADMM_RESET_RHO) {
-    std::vector<double> r((size_t)B, h->cfg.admm_rho);
-    HIPCHK(hipMemcpyAsync(a.srho, r.data(), (size_t)B * 8, hipMemcpyHostToDevice, h->stream));
-  }
+  const std::vector<double> rho((size_t)B, h->cfg.admm_rho);
+  if ((rc = admm_reset_rows(h, 0, B, what, h->stream, rho.data(), hipMemcpyHostToDevice))) return rc;
   HIPCHK(hipMemsetAsync(a.iters, 0xff, (size_t)B * I7M_MAX_SQP * sizeof(int), h->stream));
   HIPCHK(hipMemsetAsync(a.status, 0xff, (size_t)B * I7M_MAX_SQP * sizeof(int), h->stream));
-  HIPCHK(hipStreamSynchronize(h->stream));
-  return I7M_OK;
+  return i7m_synchronize(h);
 }
 
 int i7m_get_admm_stats(i7m_handle* h, int32_t B, int32_t* iters, double* rho) {
-  if (!h) return fail(I7M_EINVAL, "null handle");
-  if (h->cfg.qp_mode != I7M_QP_ADMM) return fail(I7M_EINVAL, "handle is not in I7M_QP_ADMM mode");
-  if (B < 0 || B > h->cfg.max_batch) return fail(I7M_EINVAL, "batch outside [0, max_batch]");
-  if (B == 0) return I7M_OK;
-  HIPCHK(hipSetDevice(h->dev));
-  const AdmmArgs a = admm_layout(h->d_admm, h->d_admm_it, h->cfg.max_batch, h->cfg.N, 0);
+  AdmmArgs a{};
+  const int rc = admm_rows(h, B, &a);
+  if (rc || B == 0) return rc;
   if (iters) HIPCHK(hipMemcpyAsync(iters, a.iters, (size_t)B * I7M_MAX_SQP * sizeof(int), hipMemcpyDeviceToHost, h->stream));
   if (rho) HIPCHK(hipMemcpyAsync(rho, a.srho, (size_t)B * 8, hipMemcpyDeviceToHost, h->stream));
-  HIPCHK(hipStreamSynchronize(h->stream));
-  return I7M_OK;
+  return i7m_synchronize(h);
 }
 
 int i7m_get_admm_status(i7m_handle* h, int32_t B, int32_t* status) {
   if (!h || !status) return fail(I7M_EINVAL, "null handle or output");
-  if (h->cfg.qp_mode != I7M_QP_ADMM) return fail(I7M_EINVAL, "handle is not in I7M_QP_ADMM mode");
-  if (B < 0 || B > h->cfg.max_batch) return fail(I7M_EINVAL, "batch outside [0, max_batch]");
-  if (B == 0) return I7M_OK;
-  HIPCHK(hipSetDevice(h->dev));
-  const AdmmArgs a = admm_layout(h->d_admm, h->d_admm_it, h->cfg.max_batch, h->cfg.N, 0);
+  AdmmArgs a{};
+  const int rc = admm_rows(h, B, &a);
+  if (rc || B == 0) return rc;
   HIPCHK(hipMemcpyAsync(status, a.status, (size_t)B * I7M_MAX_SQP * sizeof(int), hipMemcpyDeviceToHost, h->stream));
-  HIPCHK(hipStreamSynchronize(h->stream));
-  return I7M_OK;
+  return i7m_synchronize(h);
 }
 
 int i7m_get_admm_dual(i7m_handle* h, int32_t B, double* y) {
   if (!h || !y) return fail(I7M_EINVAL, "null handle or output");
-  if (h->cfg.qp_mode != I7M_QP_ADMM) return fail(I7M_EINVAL, "handle is not in I7M_QP_ADMM mode");
-  if (B < 0 || B > h->cfg.max_batch) return fail(I7M_EINVAL, "batch outside [0, max_batch]");
-  if (B == 0) return I7M_OK;
-  HIPCHK(hipSetDevice(h->dev));
-  const long m = 12 * (long)h->cfg.N;
-  const AdmmArgs a = admm_layout(h->d_admm, h->d_admm_it, h->cfg.max_batch, h->cfg.N, 0);
+  AdmmArgs a{};
+  int rc = admm_rows(h, B, &a);
+  if (rc || B == 0) return rc;
+  const long m = 12 * h->N;
   std::vector<double> e((size_t)B * m), c((size_t)B);
-  int rc;
   if ((rc = copy_out(h, y, a.sy, (size_t)B * m)) || (rc = copy_out(h, e.data(), a.E, (size_t)B * m)) ||
       (rc = copy_out(h, c.data(), a.cs, (size_t)B)))
     return rc;
@@ -1192,21 +1354,16 @@ int i7m_get_admm_dual(i7m_handle* h, int32_t B, double* y) {
 }
 
 int i7m_get_admm_state(i7m_handle* h, int32_t B, double* x, double* z, double* y, double* q, double* rho) {
-  if (!h) return fail(I7M_EINVAL, "null handle");
-  if (h->cfg.qp_mode != I7M_QP_ADMM) return fail(I7M_EINVAL, "handle is not in I7M_QP_ADMM mode");
-  if (B < 0 || B > h->cfg.max_batch) return fail(I7M_EINVAL, "batch outside [0, max_batch]");
-  if (B == 0) return I7M_OK;
-  HIPCHK(hipSetDevice(h->dev));
-  const long N = h->cfg.N, T = 18 * N - 6, m = 12 * N;
-  const AdmmArgs a = admm_layout(h->d_admm, h->d_admm_it, h->cfg.max_batch, N, 0);
-  int rc;
+  AdmmArgs a{};
+  int rc = admm_rows(h, B, &a);
+  if (rc || B == 0) return rc;
+  const size_t T = h->T, m = 12 * (size_t)h->N;
   if (x && (rc = copy_out(h, x, a.sx, (size_t)B * T))) return rc;
   if (z && (rc = copy_out(h, z, a.sz, (size_t)B * m))) return rc;
   if (y && (rc = copy_out(h, y, a.sy, (size_t)B * m))) return rc;
   if (q && (rc = copy_out(h, q, a.sq, (size_t)B * T))) return rc;
   if (rho && (rc = copy_out(h, rho, a.srho, (size_t)B))) return rc;
-  HIPCHK(hipStreamSynchronize(h->stream));
-  return I7M_OK;
+  return i7m_synchronize(h);
 }
 
 int i7m_synchronize(i7m_handle* h) {
@@ -1215,125 +1372,61 @@ int i7m_synchronize(i7m_handle* h) {
   return I7M_OK;
 }
 
-extern "C++" {  // (C++ helpers inside the C-ABI block)
-// The batch as two contiguous ranges (stagger_cut) on cs[0] and cs[1], the second started when the
-// first has passed its mark (the first run_sqp of its `body` records it; StaggerMark), both
-// forked from and joined back into h->stream.  body(lo, n, stream, mark) enqueues the work of
-// problems [lo, lo + n).  Results are the one-range run's: the problems are independent.
-// cut: where the second range begins; -1 = stagger_cut(B) (a caller whose problems come in groups
-// passes a cut that splits none).
-template <class Body>
-static int run_staggered(i7m_handle* h, int B, Body&& body, long cut = -1) {
-  const long cuts[3] = {0, cut < 0 ? stagger_cut(B) : cut, B};
-  StaggerMark mark{h->ev_rmark, h->tune.admm_stagger, false};
-  HIPCHK(hipEventRecord(h->ev_order, h->stream));
-  for (int r = 0; r < 2; ++r) {
-    const long lo = cuts[r], hi = cuts[r + 1];
-    HIPCHK(hipStreamWaitEvent(h->cs[r], h->ev_order, 0));
-    if (hi <= lo) continue;
-    if (r == 1 && mark.recorded) HIPCHK(hipStreamWaitEvent(h->cs[1], mark.ev, 0));
-    const int rc = body(lo, (int)(hi - lo), h->cs[r], r == 0 ? &mark : nullptr);
-    if (rc) {
-      // join the ranges already started back into h->stream before the error returns (ADVICE r5):
-      // the caller's cleanup after a synchronize of h->stream must not race them
-      const std::string msg = g_err;
-      for (int q = 0; q <= r; ++q) {
-        (void)hipEventRecord(h->ev_done[q], h->cs[q]);
-        (void)hipStreamWaitEvent(h->stream, h->ev_done[q], 0);
-      }
-      g_err = msg;
-      return rc;
-    }
-  }
-  for (int r = 0; r < 2; ++r) {
-    HIPCHK(hipEventRecord(h->ev_done[r], h->cs[r]));
-    HIPCHK(hipStreamWaitEvent(h->stream, h->ev_done[r], 0));
-  }
-  return I7M_OK;
-}
-}  // extern "C++"
-
 int i7m_solve_device(i7m_handle* h, int32_t B, const double* d_xu_in, const double* d_xcur, const double* d_goals,
                      int32_t goal_stride, double* d_xu_out, i7m_problem_stats* d_stats) {
-  int rc = check_batch(h, B, goal_stride);
-  if (rc) return rc;
-  if (B == 0) return I7M_OK;
-  if (!d_xu_in || !d_xcur || !d_goals || !d_xu_out) return fail(I7M_EINVAL, "null device pointer");
-  HIPCHK(hipSetDevice(h->dev));
+  int rc = open_batch(h, B, goal_stride, d_xu_in && d_xcur && d_goals && d_xu_out, "null device pointer");
+  if (rc || B == 0) return rc;
   ProblemStats* st = d_stats ? reinterpret_cast<ProblemStats*>(d_stats) : h->d_stats;
-  if (stagger_applies(h->tune, h->cfg.qp_mode, B)) {
-    const size_t T = 18 * (size_t)h->cfg.N - 6, N = h->cfg.N;
-    return run_staggered(h, B, [&](long lo, int n, hipStream_t s, StaggerMark* mark) {
-      return run_sqp(h, n, d_xu_in + lo * T, d_xu_out + lo * T, d_xcur + lo * 12, d_goals + lo * N * goal_stride,
-                     goal_stride, st + lo, lo, s, mark);
-    });
-  }
-  return run_sqp_graphed(h, B, d_xu_in, d_xu_out, d_xcur, d_goals, goal_stride, st);
+  return run_ranges(h, B, [&](long lo, int n, hipStream_t s, StaggerMark* mark) {
+    // the whole batch on the handle's stream goes through the graph cache
+    if (s == h->stream) return run_sqp_graphed(h, B, d_xu_in, d_xu_out, d_xcur, d_goals, goal_stride, st);
+    return run_sqp(h, n, d_xu_in + lo * h->T, d_xu_out + lo * h->T, d_xcur + lo * 12, d_goals + lo * h->N * goal_stride,
+                   goal_stride, st + lo, lo, s, mark);
+  });
 }
 
 int i7m_solve(i7m_handle* h, int32_t B, const double* xu_in, const double* xcur, const double* goals,
               int32_t goal_stride, double* xu_out, i7m_problem_stats* stats) {
-  int rc = check_batch(h, B, goal_stride);
-  if (rc) return rc;
-  if (B == 0) return I7M_OK;
-  if (!xu_in || !xcur || !goals || !xu_out) return fail(I7M_EINVAL, "null pointer");
-  HIPCHK(hipSetDevice(h->dev));
-  const size_t T = 18 * (size_t)h->cfg.N - 6, N = h->cfg.N;
+  int rc = open_batch(h, B, goal_stride, xu_in && xcur && goals && xu_out);
+  if (rc || B == 0) return rc;
   const int nch = h2h_chunks_for(h->tune, h->cfg.qp_mode, B);
   if (nch > 1) return solve_h2h_chunked(h, B, xu_in, xcur, goals, goal_stride, xu_out, stats, nch);
-  if ((rc = copy_in(h, h->d_xu, xu_in, (size_t)B * T))) return rc;
-  if ((rc = copy_in(h, h->d_xs, xcur, (size_t)B * 12))) return rc;
-  if ((rc = copy_in(h, h->d_goal, goals, (size_t)B * N * goal_stride))) return rc;
+  if ((rc = stage_in(h, 0, B, xu_in, xcur, goals, goal_stride))) return rc;
   if ((rc = run_sqp_graphed(h, B, h->d_xu, h->d_xu, h->d_xs, h->d_goal, goal_stride, h->d_stats))) return rc;
-  if ((rc = copy_out(h, xu_out, h->d_xu, (size_t)B * T))) return rc;
-  if (stats)
-    HIPCHK(hipMemcpyAsync(stats, h->d_stats, sizeof(ProblemStats) * (size_t)B, hipMemcpyDeviceToHost, h->stream));
-  HIPCHK(hipStreamSynchronize(h->stream));
-  return I7M_OK;
+  if ((rc = stage_out(h, 0, B, xu_out, stats))) return rc;
+  return i7m_synchronize(h);
 }
 
 int i7m_qp(i7m_handle* h, int32_t B, const double* xu, const double* xcur, const double* goals, int32_t goal_stride,
            double* sol) {
-  int rc = check_batch(h, B, goal_stride);
-  if (rc) return rc;
-  if (B == 0) return I7M_OK;
-  if (!xu || !xcur || !goals || !sol) return fail(I7M_EINVAL, "null pointer");
-  HIPCHK(hipSetDevice(h->dev));
-  const size_t T = 18 * (size_t)h->cfg.N - 6, N = h->cfg.N;
-  SolveParams P = params_of(h, B, goal_stride);
-  if ((rc = copy_in(h, h->d_xu, xu, (size_t)B * T))) return rc;
-  if ((rc = copy_in(h, h->d_xs, xcur, (size_t)B * 12))) return rc;
-  if ((rc = copy_in(h, h->d_goal, goals, (size_t)B * N * goal_stride))) return rc;
-  if ((rc = launch_linearize(h, h->stream, bufs_at(h, 0), P, h->d_xu, h->d_goal, nullptr))) return rc;
+  int rc = open_batch(h, B, goal_stride, xu && xcur && goals && sol);
+  if (rc || B == 0) return rc;
+  const SolveParams P = params_of(h, B, goal_stride);
+  const Bufs W = bufs_at(h, 0);
+  if ((rc = stage_in(h, 0, B, xu, xcur, goals, goal_stride))) return rc;
+  if ((rc = launch_linearize(h, h->stream, W, P, h->d_xu, h->d_goal, nullptr))) return rc;
   const double* qsol = nullptr;
-  if ((rc = solve_qp(h, h->stream, bufs_at(h, 0), P, h->d_xu, h->d_xs, nullptr, h->d_sol, &qsol))) return rc;
-  if ((rc = copy_out(h, sol, qsol, (size_t)B * T))) return rc;
-  HIPCHK(hipStreamSynchronize(h->stream));
-  return I7M_OK;
+  if ((rc = solve_qp(h, h->stream, W, P, h->d_xu, h->d_xs, nullptr, W.sol, &qsol))) return rc;
+  if ((rc = copy_out(h, sol, qsol, (size_t)B * h->T))) return rc;
+  return i7m_synchronize(h);
 }
 
 int i7m_qp_value(i7m_handle* h, int32_t B, const double* xu, const double* xcur, const double* goals, int32_t goal_stride,
                  double* V0) {
-  int rc = check_batch(h, B, goal_stride);
-  if (rc) return rc;
-  if (B == 0) return I7M_OK;
-  if (!xu || !xcur || !goals || !V0) return fail(I7M_EINVAL, "null pointer");
+  int rc = open_batch(h, B, goal_stride, xu && xcur && goals && V0);
+  if (rc || B == 0) return rc;
   if (h->cfg.qp_mode != I7M_QP_DIRECT) return fail(I7M_EINVAL, "i7m_qp_value: the equality-constrained QP only");
-  const size_t T = 18 * (size_t)h->cfg.N - 6, N = h->cfg.N;
   // (B x 169 doubles in the solution buffer: T = 18 N - 6 >= 169 from N = 10) — a precondition,
   // checked before any copy or launch
-  if (T < 169) return fail(I7M_EINVAL, "i7m_qp_value needs N >= 10");
-  HIPCHK(hipSetDevice(h->dev));
-  SolveParams P = params_of(h, B, goal_stride);
-  if ((rc = copy_in(h, h->d_xu, xu, (size_t)B * T))) return rc;
-  if ((rc = copy_in(h, h->d_xs, xcur, (size_t)B * 12))) return rc;
-  if ((rc = copy_in(h, h->d_goal, goals, (size_t)B * N * goal_stride))) return rc;
-  if ((rc = launch_linearize(h, h->stream, bufs_at(h, 0), P, h->d_xu, h->d_goal, nullptr))) return rc;
-  double* vbuf = h->d_sol;
-  if ((rc = launch_riccati(h, h->stream, bufs_at(h, 0), P, h->d_xu, h->d_xs, nullptr, h->d_sol, vbuf))) return rc;
+  if (h->T < 169) return fail(I7M_EINVAL, "i7m_qp_value needs N >= 10");
+  const SolveParams P = params_of(h, B, goal_stride);
+  const Bufs W = bufs_at(h, 0);
+  if ((rc = stage_in(h, 0, B, xu, xcur, goals, goal_stride))) return rc;
+  if ((rc = launch_linearize(h, h->stream, W, P, h->d_xu, h->d_goal, nullptr))) return rc;
+  double* vbuf = W.sol;
+  if ((rc = launch_riccati(h, h->stream, W, P, h->d_xu, h->d_xs, nullptr, W.sol, vbuf))) return rc;
   if ((rc = copy_out(h, V0, vbuf, (size_t)B * 169))) return rc;
-  HIPCHK(hipStreamSynchronize(h->stream));
-  return I7M_OK;
+  return i7m_synchronize(h);
 }
 
 int i7m_get_box_stats(i7m_handle* h, int32_t B, int32_t* iters, int32_t* converged, double* mu) {
@@ -1354,110 +1447,65 @@ int i7m_get_box_stats(i7m_handle* h, int32_t B, int32_t* iters, int32_t* converg
 
 int i7m_linearize(i7m_handle* h, int32_t B, const double* xu, const double* goals, int32_t goal_stride, double* lin,
                   double* cost) {
-  int rc = check_batch(h, B, goal_stride);
-  if (rc) return rc;
-  if (B == 0) return I7M_OK;
-  if (!xu || !goals) return fail(I7M_EINVAL, "null pointer");
-  HIPCHK(hipSetDevice(h->dev));
-  const size_t T = 18 * (size_t)h->cfg.N - 6, N = h->cfg.N;
-  SolveParams P = params_of(h, B, goal_stride);
-  if ((rc = copy_in(h, h->d_xu, xu, (size_t)B * T))) return rc;
-  if ((rc = copy_in(h, h->d_goal, goals, (size_t)B * N * goal_stride))) return rc;
+  int rc = open_batch(h, B, goal_stride, xu && goals);
+  if (rc || B == 0) return rc;
+  const size_t N = h->N;
+  const SolveParams P = params_of(h, B, goal_stride);
+  if ((rc = stage_in(h, 0, B, xu, nullptr, goals, goal_stride))) return rc;
   if ((rc = launch_linearize(h, h->stream, bufs_at(h, 0), P, h->d_xu, h->d_goal, nullptr))) return rc;
   if (lin && (rc = copy_out(h, lin, h->d_lin, (size_t)B * (N - 1) * LIN_STRIDE))) return rc;
   if (cost && (rc = copy_out(h, cost, h->d_cost, (size_t)B * N * COST_STRIDE))) return rc;
-  HIPCHK(hipStreamSynchronize(h->stream));
-  return I7M_OK;
+  return i7m_synchronize(h);
 }
 
 int i7m_merit(i7m_handle* h, int32_t B, const double* xu, const double* xu_ref, const double* goals,
               int32_t goal_stride, double* out) {
-  int rc = check_batch(h, B, goal_stride);
-  if (rc) return rc;
-  if (B == 0) return I7M_OK;
-  if (!xu || !xu_ref || !goals || !out) return fail(I7M_EINVAL, "null pointer");
-  HIPCHK(hipSetDevice(h->dev));
-  const size_t T = 18 * (size_t)h->cfg.N - 6, N = h->cfg.N;
-  SolveParams P = params_of(h, B, goal_stride);
-  if ((rc = copy_in(h, h->d_xu, xu, (size_t)B * T))) return rc;
-  if ((rc = copy_in(h, h->d_aux, xu_ref, (size_t)B * T))) return rc;
-  if ((rc = copy_in(h, h->d_goal, goals, (size_t)B * N * goal_stride))) return rc;
+  int rc = open_batch(h, B, goal_stride, xu && xu_ref && goals && out);
+  if (rc || B == 0) return rc;
+  const SolveParams P = params_of(h, B, goal_stride);
+  if ((rc = stage_in(h, 0, B, xu, nullptr, goals, goal_stride))) return rc;
+  if ((rc = copy_in(h, h->d_aux, xu_ref, (size_t)B * h->T))) return rc;
   hipLaunchKernelGGL(k_merit, dim3(B), dim3(64), 0, h->stream, h->d_model, P, h->d_xu, h->d_aux, h->d_goal,
                      h->has_fext ? h->d_fext : nullptr, (int)(h->fext_frame == I7M_WRENCH_WORLD), h->d_out);
   HIPCHK(hipGetLastError());
   if ((rc = copy_out(h, out, h->d_out, (size_t)B * 5))) return rc;
-  HIPCHK(hipStreamSynchronize(h->stream));
-  return I7M_OK;
+  return i7m_synchronize(h);
 }
 
 int i7m_linesearch(i7m_handle* h, int32_t B, const double* xu, const double* xu_full, const double* goals,
                    int32_t goal_stride, double* alpha) {
-  int rc = check_batch(h, B, goal_stride);
-  if (rc) return rc;
-  if (B == 0) return I7M_OK;
-  if (!xu || !xu_full || !goals || !alpha) return fail(I7M_EINVAL, "null pointer");
-  HIPCHK(hipSetDevice(h->dev));
-  const size_t T = 18 * (size_t)h->cfg.N - 6, N = h->cfg.N;
-  SolveParams P = params_of(h, B, goal_stride);
-  if ((rc = copy_in(h, h->d_xu, xu, (size_t)B * T))) return rc;
-  if ((rc = copy_in(h, h->d_sol, xu_full, (size_t)B * T))) return rc;
-  if ((rc = copy_in(h, h->d_goal, goals, (size_t)B * N * goal_stride))) return rc;
-  if ((rc = launch_linesearch(h, h->stream, bufs_at(h, 0), P, h->d_xu, h->d_xu, h->d_sol, h->d_goal, nullptr, h->d_stats, h->d_out, 0, 1,
-                             false))) return rc;
+  int rc = open_batch(h, B, goal_stride, xu && xu_full && goals && alpha);
+  if (rc || B == 0) return rc;
+  const SolveParams P = params_of(h, B, goal_stride);
+  if ((rc = stage_in(h, 0, B, xu, nullptr, goals, goal_stride))) return rc;
+  if ((rc = copy_in(h, h->d_sol, xu_full, (size_t)B * h->T))) return rc;
+  if ((rc = launch_linesearch(h, h->stream, bufs_at(h, 0), P, h->d_xu, h->d_xu, h->d_sol, h->d_goal, nullptr, h->d_stats,
+                              h->d_out, 0, 1, false)))
+    return rc;
   if ((rc = copy_out(h, alpha, h->d_out, (size_t)B))) return rc;
-  HIPCHK(hipStreamSynchronize(h->stream));
-  return I7M_OK;
+  return i7m_synchronize(h);
 }
 
-// ---- query hooks: chunk through the max_batch*T-sized scratch buffers ----------------------
-static size_t scratch_doubles(const i7m_handle* h) {
-  return std::max((size_t)h->cfg.max_batch * (18 * (size_t)h->cfg.N - 6), (size_t)256 * 114);
-}
-static size_t query_cap(const i7m_handle* h) { return scratch_doubles(h) / 36; }  // <= 36 doubles/query
-
+// ---- query hooks: chunk through the scratch buffers (query_chunks), <= 36 doubles per query and
+// buffer, 114 for the derivatives' outputs ---------------------------------------------------------
 int i7m_eepos(i7m_handle* h, int32_t Bq, const double* q, double* p_out, double* J_out) {
   if (!h) return fail(I7M_EINVAL, "null handle");
   if (Bq < 0 || !q || !p_out) return fail(I7M_EINVAL, "bad arguments");
-  HIPCHK(hipSetDevice(h->dev));
-  const size_t cap = query_cap(h);
-  int rc;
-  for (size_t o = 0; o < (size_t)Bq; o += cap) {
-    const int n = (int)std::min(cap, (size_t)Bq - o);
-    if ((rc = copy_in(h, h->d_aux, q + 6 * o, 6 * (size_t)n))) return rc;
-    hipLaunchKernelGGL(k_eepos, dim3((n + 255) / 256), dim3(256), 0, h->stream, h->d_model, n, h->d_aux, h->d_sol,
-                       J_out ? h->d_out : nullptr);
-    HIPCHK(hipGetLastError());
-    if ((rc = copy_out(h, p_out + 3 * o, h->d_sol, 3 * (size_t)n))) return rc;
-    if (J_out && (rc = copy_out(h, J_out + 18 * o, h->d_out, 18 * (size_t)n))) return rc;
-    HIPCHK(hipStreamSynchronize(h->stream));
-  }
-  return I7M_OK;
+  return query_chunks(h, Bq, 36, {{q, 6}}, {{p_out, 3}, {J_out, 18, h->d_out}}, [&](int n, double** in, double** out) {
+    hipLaunchKernelGGL(k_eepos, dim3((n + 255) / 256), dim3(256), 0, h->stream, h->d_model, n, in[0], out[0],
+                       J_out ? out[1] : nullptr);
+  });
 }
 
 int i7m_aba(i7m_handle* h, int32_t Bq, const double* q, const double* v, const double* tau, const double* fext,
             int32_t frame, double* a_out) {
   if (!h) return fail(I7M_EINVAL, "null handle");
   if (Bq < 0 || !q || !v || !tau || !a_out) return fail(I7M_EINVAL, "bad arguments");
-  HIPCHK(hipSetDevice(h->dev));
-  const size_t cap = query_cap(h);
-  int rc;
-  for (size_t o = 0; o < (size_t)Bq; o += cap) {
-    const int n = (int)std::min(cap, (size_t)Bq - o);
-    double* dq = h->d_aux;
-    double* dv = h->d_aux + 6 * (size_t)n;
-    double* dtau = h->d_aux + 12 * (size_t)n;
-    double* df = h->d_aux + 18 * (size_t)n;
-    if ((rc = copy_in(h, dq, q + 6 * o, 6 * (size_t)n))) return rc;
-    if ((rc = copy_in(h, dv, v + 6 * o, 6 * (size_t)n))) return rc;
-    if ((rc = copy_in(h, dtau, tau + 6 * o, 6 * (size_t)n))) return rc;
-    if (fext && (rc = copy_in(h, df, fext + 6 * o, 6 * (size_t)n))) return rc;
-    hipLaunchKernelGGL(k_aba, dim3((n + 255) / 256), dim3(256), 0, h->stream, h->d_model, n, dq, dv, dtau,
-                       fext ? df : nullptr, (int)(frame == I7M_WRENCH_WORLD), h->d_sol);
-    HIPCHK(hipGetLastError());
-    if ((rc = copy_out(h, a_out + 6 * o, h->d_sol, 6 * (size_t)n))) return rc;
-    HIPCHK(hipStreamSynchronize(h->stream));
-  }
-  return I7M_OK;
+  const auto launch = [&](int n, double** in, double** out) {
+    hipLaunchKernelGGL(k_aba, dim3((n + 255) / 256), dim3(256), 0, h->stream, h->d_model, n, in[0], in[1], in[2],
+                       fext ? in[3] : nullptr, (int)(frame == I7M_WRENCH_WORLD), out[0]);
+  };
+  return query_chunks(h, Bq, 36, {{q, 6}, {v, 6}, {tau, 6}, {fext, 6}}, {{a_out, 6}}, launch);
 }
 
 int i7m_aba_derivatives(i7m_handle* h, int32_t Bq, const double* q, const double* v, const double* tau, double* dq_out,
@@ -1465,62 +1513,25 @@ int i7m_aba_derivatives(i7m_handle* h, int32_t Bq, const double* q, const double
   if (!h) return fail(I7M_EINVAL, "null handle");
   if (Bq < 0 || !q || !v || !tau || !dq_out || !dv_out || !Minv_out || !a_out)
     return fail(I7M_EINVAL, "bad arguments");
-  HIPCHK(hipSetDevice(h->dev));
-  // outputs need 3*36+6 doubles per query: put them in d_out/d_sol/d_lin regions
-  const size_t cap = scratch_doubles(h) / 114;
-  int rc;
-  for (size_t o = 0; o < (size_t)Bq; o += cap) {
-    const int n = (int)std::min(cap, (size_t)Bq - o);
-    double* iq = h->d_aux;
-    double* iv = h->d_aux + 6 * (size_t)n;
-    double* it = h->d_aux + 12 * (size_t)n;
-    double* oq = h->d_sol;
-    double* ov = h->d_sol + 36 * (size_t)n;
-    double* om = h->d_sol + 72 * (size_t)n;
-    double* oa = h->d_sol + 108 * (size_t)n;
-    if ((rc = copy_in(h, iq, q + 6 * o, 6 * (size_t)n))) return rc;
-    if ((rc = copy_in(h, iv, v + 6 * o, 6 * (size_t)n))) return rc;
-    if ((rc = copy_in(h, it, tau + 6 * o, 6 * (size_t)n))) return rc;
+  const auto launch = [&](int n, double** in, double** out) {
     const long nthr = 12L * n;
-    hipLaunchKernelGGL(k_abad, dim3((unsigned)((nthr + 255) / 256)), dim3(256), 0, h->stream, h->d_model, n, iq, iv,
-                       it, oq, ov, om, oa);
-    HIPCHK(hipGetLastError());
-    if ((rc = copy_out(h, dq_out + 36 * o, oq, 36 * (size_t)n))) return rc;
-    if ((rc = copy_out(h, dv_out + 36 * o, ov, 36 * (size_t)n))) return rc;
-    if ((rc = copy_out(h, Minv_out + 36 * o, om, 36 * (size_t)n))) return rc;
-    if ((rc = copy_out(h, a_out + 6 * o, oa, 6 * (size_t)n))) return rc;
-    HIPCHK(hipStreamSynchronize(h->stream));
-  }
-  return I7M_OK;
+    hipLaunchKernelGGL(k_abad, dim3((unsigned)((nthr + 255) / 256)), dim3(256), 0, h->stream, h->d_model, n, in[0], in[1],
+                       in[2], out[0], out[1], out[2], out[3]);
+  };
+  // the outputs need 3*36+6 doubles per query
+  return query_chunks(h, Bq, 114, {{q, 6}, {v, 6}, {tau, 6}}, {{dq_out, 36}, {dv_out, 36}, {Minv_out, 36}, {a_out, 6}},
+                      launch);
 }
 
 int i7m_rk4(i7m_handle* h, int32_t Bq, const double* q, const double* v, const double* u, double dt,
             const double* fext, int32_t frame, double* q_out, double* v_out) {
   if (!h) return fail(I7M_EINVAL, "null handle");
   if (Bq < 0 || !q || !v || !u || !q_out || !v_out) return fail(I7M_EINVAL, "bad arguments");
-  HIPCHK(hipSetDevice(h->dev));
-  const size_t cap = query_cap(h);
-  int rc;
-  for (size_t o = 0; o < (size_t)Bq; o += cap) {
-    const int n = (int)std::min(cap, (size_t)Bq - o);
-    double* iq = h->d_aux;
-    double* iv = h->d_aux + 6 * (size_t)n;
-    double* iu = h->d_aux + 12 * (size_t)n;
-    double* iff = h->d_aux + 18 * (size_t)n;
-    double* oq = h->d_sol;
-    double* ov = h->d_sol + 6 * (size_t)n;
-    if ((rc = copy_in(h, iq, q + 6 * o, 6 * (size_t)n))) return rc;
-    if ((rc = copy_in(h, iv, v + 6 * o, 6 * (size_t)n))) return rc;
-    if ((rc = copy_in(h, iu, u + 6 * o, 6 * (size_t)n))) return rc;
-    if (fext && (rc = copy_in(h, iff, fext + 6 * o, 6 * (size_t)n))) return rc;
-    hipLaunchKernelGGL(k_rk4, dim3((n + 255) / 256), dim3(256), 0, h->stream, h->d_model, n, iq, iv, iu, dt,
-                       fext ? iff : nullptr, (int)(frame == I7M_WRENCH_WORLD), oq, ov);
-    HIPCHK(hipGetLastError());
-    if ((rc = copy_out(h, q_out + 6 * o, oq, 6 * (size_t)n))) return rc;
-    if ((rc = copy_out(h, v_out + 6 * o, ov, 6 * (size_t)n))) return rc;
-    HIPCHK(hipStreamSynchronize(h->stream));
-  }
-  return I7M_OK;
+  const auto launch = [&](int n, double** in, double** out) {
+    hipLaunchKernelGGL(k_rk4, dim3((n + 255) / 256), dim3(256), 0, h->stream, h->d_model, n, in[0], in[1], in[2], dt,
+                       fext ? in[3] : nullptr, (int)(frame == I7M_WRENCH_WORLD), out[0], out[1]);
+  };
+  return query_chunks(h, Bq, 36, {{q, 6}, {v, 6}, {u, 6}, {fext, 6}}, {{q_out, 6}, {v_out, 6}}, launch);
 }
 
 int i7m_mpc_run(i7m_handle* h, int32_t B, const double* xstart, const double* endpoints, int32_t n_endpoints,
@@ -1536,76 +1547,48 @@ int i7m_mpc_run(i7m_handle* h, int32_t B, const double* xstart, const double* en
                             "(clear it with i7m_set_external_wrench(h, 0, NULL, 0))");
   if (B == 0) return I7M_OK;
   HIPCHK(hipSetDevice(h->dev));
-  const int N = h->cfg.N;
-  const size_t T = 18 * (size_t)N - 6;
+  const int N = (int)h->N;
+  const size_t T = h->T;
   // per-run state beyond the handle's buffers (this is a whole closed-loop run, not the solve
   // hot path): endpoints, goal index, alive flag, the distance and q histories
-  double *d_ep = nullptr, *d_dist = nullptr, *d_q = nullptr;
-  int *d_gi = nullptr, *d_alive = nullptr;
-  auto cleanup = [&]() {
-    for (void* p : {(void*)d_ep, (void*)d_dist, (void*)d_q, (void*)d_gi, (void*)d_alive})
-      if (p) (void)hipFree(p);
-  };
-  const size_t hist = (size_t)std::max(num_steps, 1) * B;
-  if (hipMalloc(&d_ep, 3 * 8 * (size_t)n_endpoints) != hipSuccess || hipMalloc(&d_dist, 8 * hist) != hipSuccess ||
-      hipMalloc(&d_q, 6 * 8 * hist) != hipSuccess || hipMalloc(&d_gi, 4 * (size_t)B) != hipSuccess ||
-      hipMalloc(&d_alive, 4 * (size_t)B) != hipSuccess) {
-    cleanup();
-    return fail(I7M_ENOMEM, "mpc_run: device allocation failed");
-  }
-  auto run = [&]() -> int {
-    // src/osqp_mpc.py:14-27: goal = endpoint 0 tiled, XU = 0, XU = sqp(xcur, goal, XU)
-    std::vector<double> goals((size_t)B * 3 * N);
-    for (size_t b = 0; b < (size_t)B; ++b)
-      for (int k = 0; k < N; ++k)
-        for (int r = 0; r < 3; ++r) goals[(b * N + k) * 3 + r] = endpoints[r];
-    std::vector<int> ones((size_t)B, 1);
-    int rc2;
-    if ((rc2 = copy_in(h, h->d_xs, xstart, (size_t)B * 12))) return rc2;
-    if ((rc2 = copy_in(h, h->d_goal, goals.data(), goals.size()))) return rc2;
-    if ((rc2 = copy_in(h, d_ep, endpoints, 3 * (size_t)n_endpoints))) return rc2;
-    HIPCHK(hipMemsetAsync(d_gi, 0, 4 * (size_t)B, h->stream));
-    HIPCHK(hipMemcpyAsync(d_alive, ones.data(), 4 * (size_t)B, hipMemcpyHostToDevice, h->stream));
-    HIPCHK(hipMemsetAsync(h->d_xu, 0, 8 * (size_t)B * T, h->stream));
-    // the instances [lo, lo + n) through every MPC step on stream s (the whole batch on the
-    // handle's stream, or, where the solve staggers, each range on its own: the instances are
-    // independent, so a range runs its steps without waiting for the other; its first solve
-    // records the staggered ranges' mark)
-    auto loop = [&](long lo, int n, hipStream_t s, StaggerMark* mark) -> int {
-      const double* xu0 = h->d_xu + lo * T;
-      double *xu = h->d_xu + lo * T, *out = h->d_out + lo * T, *xs = h->d_xs + lo * 12, *g = h->d_goal + lo * 3 * N;
-      int rc3;
-      if ((rc3 = run_sqp(h, n, xu0, xu, xs, g, 3, h->d_stats + lo, lo, s, mark))) return rc3;
-      for (int i = 0; i < num_steps; ++i) {
-        hipLaunchKernelGGL(k_mpc_goal, dim3((n + 255) / 256), dim3(256), 0, s, h->d_model, n, N, xs, g, d_ep, n_endpoints,
-                           d_gi + lo, d_alive + lo, d_dist + (size_t)i * B + lo);
-        HIPCHK(hipGetLastError());
-        // xu_new = sqp(xcur, goal, XU) into the scratch buffer d_out (XU itself is read only)
-        if ((rc3 = run_sqp(h, n, xu, out, xs, g, 3, h->d_stats + lo, lo, s))) return rc3;
-        hipLaunchKernelGGL(k_mpc_advance, dim3(n), dim3(64), 0, s, h->d_model, n, N, h->cfg.dt, xs, xu, out, d_alive + lo,
-                           d_q + ((size_t)i * B + lo) * 6);
-        HIPCHK(hipGetLastError());
-      }
-      return I7M_OK;
-    };
-    if (stagger_applies(h->tune, h->cfg.qp_mode, B)) {
-      if ((rc2 = run_staggered(h, B, loop))) return rc2;
-    } else if ((rc2 = loop(0, B, h->stream, nullptr))) {
-      return rc2;
+  size_t bytes[MPC_WS_COUNT];
+  mpc_ws_bytes(B, n_endpoints, num_steps, bytes);
+  const LoopStart start(h, B, B, endpoints);  // (declared first: destroyed after the workspace's synchronize)
+  Workspace ws(h, bytes);
+  if (!ws.base) return fail(I7M_ENOMEM, "mpc_run: device allocation failed");
+  double *d_ep = ws.at<double>(MPC_WS_EP), *d_dist = ws.at<double>(MPC_WS_DIST), *d_q = ws.at<double>(MPC_WS_Q);
+  int *d_gi = ws.at<int>(MPC_WS_GI), *d_alive = ws.at<int>(MPC_WS_ALIVE);
+  // src/osqp_mpc.py:14-27: goal = endpoint 0 tiled, XU = 0, XU = sqp(xcur, goal, XU)
+  if ((rc = copy_in(h, h->d_xs, xstart, (size_t)B * 12))) return rc;
+  if ((rc = loop_start(h, start, endpoints, n_endpoints, d_ep, d_gi, d_alive))) return rc;
+  // the instances [lo, lo + n) through every MPC step on stream s (the whole batch on the
+  // handle's stream, or, where the solve staggers, each range on its own: the instances are
+  // independent, so a range runs its steps without waiting for the other; its first solve
+  // records the staggered ranges' mark)
+  rc = run_ranges(h, B, [&](long lo, int n, hipStream_t s, StaggerMark* mark) -> int {
+    double *xu = h->d_xu + lo * T, *out = h->d_out + lo * T, *xs = h->d_xs + lo * 12, *g = h->d_goal + lo * 3 * N;
+    int rc3;
+    if ((rc3 = run_sqp(h, n, xu, xu, xs, g, 3, nullptr, lo, s, mark))) return rc3;
+    for (int i = 0; i < num_steps; ++i) {
+      hipLaunchKernelGGL(k_mpc_goal, dim3((n + 255) / 256), dim3(256), 0, s, h->d_model, n, N, xs, g, d_ep, n_endpoints,
+                         d_gi + lo, d_alive + lo, d_dist + (size_t)i * B + lo);
+      HIPCHK(hipGetLastError());
+      // xu_new = sqp(xcur, goal, XU) into the scratch buffer d_out (XU itself is read only)
+      if ((rc3 = run_sqp(h, n, xu, out, xs, g, 3, nullptr, lo, s))) return rc3;
+      hipLaunchKernelGGL(k_mpc_advance, dim3(n), dim3(64), 0, s, h->d_model, n, N, h->cfg.dt, xs, xu, out, d_alive + lo,
+                         d_q + ((size_t)i * B + lo) * 6);
+      HIPCHK(hipGetLastError());
     }
-    if (num_steps > 0) {
-      if ((rc2 = copy_out(h, dist_out, d_dist, (size_t)num_steps * B))) return rc2;
-      if (q_out && (rc2 = copy_out(h, q_out, d_q, (size_t)num_steps * B * 6))) return rc2;
-    }
-    if (xcur_out && (rc2 = copy_out(h, xcur_out, h->d_xs, (size_t)B * 12))) return rc2;
-    if (xu_out && (rc2 = copy_out(h, xu_out, h->d_xu, (size_t)B * T))) return rc2;
-    HIPCHK(hipStreamSynchronize(h->stream));
     return I7M_OK;
-  };
-  rc = run();
-  (void)hipStreamSynchronize(h->stream);
-  cleanup();
-  return rc;
+  });
+  if (rc) return rc;
+  if (num_steps > 0) {
+    if ((rc = copy_out(h, dist_out, d_dist, (size_t)num_steps * B))) return rc;
+    if (q_out && (rc = copy_out(h, q_out, d_q, (size_t)num_steps * B * 6))) return rc;
+  }
+  if (xcur_out && (rc = copy_out(h, xcur_out, h->d_xs, (size_t)B * 12))) return rc;
+  if (xu_out && (rc = copy_out(h, xu_out, h->d_xu, (size_t)B * T))) return rc;
+  return i7m_synchronize(h);
 }
 
 int i7m_sampled_opts_default(i7m_sampled_opts* o) {
@@ -1646,143 +1629,107 @@ int i7m_mpc_run_sampled(i7m_handle* h, int32_t G, int32_t H, const double* xstar
     return fail(I7M_EINVAL, "mpc_run_sampled: null xstart, endpoints, fhyp, f_actual or dist_out");
   if (G == 0) return I7M_OK;
   HIPCHK(hipSetDevice(h->dev));
-  const int N = h->cfg.N, B = G * H;
-  const size_t T = 18 * (size_t)N - 6;
+  const int N = (int)h->N, B = G * H;
+  const size_t T = h->T;
   const bool admm = h->cfg.qp_mode == I7M_QP_ADMM;
   // per-run state beyond the handle's buffers: per group the state, XU_best, the scored
   // hypothesis, goal index and alive flag; the schedules and the histories
-  double *d_ep = nullptr, *d_xcur = nullptr, *d_xub = nullptr, *d_fact = nullptr, *d_noise = nullptr, *d_dist = nullptr,
-         *d_q = nullptr, *d_fb = nullptr, *d_rho0 = nullptr;
-  int *d_best = nullptr, *d_gi = nullptr, *d_alive = nullptr, *d_bh = nullptr;
-  auto cleanup = [&]() {
-    for (void* p : {(void*)d_ep, (void*)d_xcur, (void*)d_xub, (void*)d_fact, (void*)d_noise, (void*)d_dist, (void*)d_q,
-                    (void*)d_fb, (void*)d_rho0, (void*)d_best, (void*)d_gi, (void*)d_alive, (void*)d_bh})
-      if (p) (void)hipFree(p);
-  };
-  const size_t hist = (size_t)std::max(num_steps, 1) * G;
-  if (hipMalloc(&d_ep, 3 * 8 * (size_t)n_endpoints) != hipSuccess || hipMalloc(&d_xcur, 12 * 8 * (size_t)G) != hipSuccess ||
-      hipMalloc(&d_xub, 8 * T * G) != hipSuccess || hipMalloc(&d_fact, 6 * 8 * (size_t)o.n_actual * G) != hipSuccess ||
-      (noise && num_steps > 0 && hipMalloc(&d_noise, 3 * 8 * (size_t)num_steps * B) != hipSuccess) ||
-      hipMalloc(&d_dist, 8 * hist) != hipSuccess || hipMalloc(&d_q, 6 * 8 * hist) != hipSuccess ||
-      hipMalloc(&d_fb, 6 * 8 * hist) != hipSuccess || hipMalloc(&d_rho0, 8 * (size_t)B) != hipSuccess ||
-      hipMalloc(&d_best, 4 * (size_t)G) != hipSuccess || hipMalloc(&d_gi, 4 * (size_t)G) != hipSuccess ||
-      hipMalloc(&d_alive, 4 * (size_t)G) != hipSuccess || hipMalloc(&d_bh, 4 * hist) != hipSuccess) {
-    cleanup();
-    return fail(I7M_ENOMEM, "mpc_run_sampled: device allocation failed");
-  }
-  // host staging, alive until the final synchronize
-  std::vector<double> goals((size_t)B * 3 * N), xrows((size_t)B * 12), rho0((size_t)B, h->cfg.admm_rho);
-  std::vector<int> ones((size_t)G, 1);
-  auto run = [&]() -> int {
-    // src/gato_mpc_batch_sample.py:111-128: goal = endpoint 0 tiled, XU = [xstart, 0...], every
-    // row of a group at the group's start state, the hypotheses set on the solver
-    for (size_t b = 0; b < (size_t)B; ++b) {
-      for (int k = 0; k < N; ++k)
-        for (int r = 0; r < 3; ++r) goals[(b * N + k) * 3 + r] = endpoints[r];
-      for (int r = 0; r < 12; ++r) xrows[b * 12 + r] = xstart[(b / H) * 12 + r];
-    }
-    int rc2;
-    if ((rc2 = copy_in(h, h->d_xs, xrows.data(), xrows.size()))) return rc2;
-    if ((rc2 = copy_in(h, d_xcur, xstart, (size_t)G * 12))) return rc2;
-    if ((rc2 = copy_in(h, h->d_goal, goals.data(), goals.size()))) return rc2;
-    if ((rc2 = copy_in(h, d_ep, endpoints, 3 * (size_t)n_endpoints))) return rc2;
-    if ((rc2 = copy_in(h, d_fact, f_actual, 6 * (size_t)o.n_actual * G))) return rc2;
-    if (d_noise && (rc2 = copy_in(h, d_noise, noise, 3 * (size_t)num_steps * B))) return rc2;
-    if ((rc2 = copy_in(h, d_rho0, rho0.data(), rho0.size()))) return rc2;
-    HIPCHK(hipMemsetAsync(h->d_xu, 0, 8 * (size_t)B * T, h->stream));
-    HIPCHK(hipMemcpy2DAsync(h->d_xu, T * 8, xrows.data(), 12 * 8, 12 * 8, (size_t)B, hipMemcpyHostToDevice, h->stream));
-    HIPCHK(hipMemsetAsync(d_gi, 0, 4 * (size_t)G, h->stream));
-    HIPCHK(hipMemsetAsync(d_best, 0, 4 * (size_t)G, h->stream));  // the initial solve's XU_best is row 0, :128
-    HIPCHK(hipMemcpyAsync(d_alive, ones.data(), 4 * (size_t)G, hipMemcpyHostToDevice, h->stream));
-    HIPCHK(hipMemsetAsync(h->d_fext, 0, (size_t)h->cfg.max_batch * 6 * 8, h->stream));
-    if ((rc2 = copy_in(h, h->d_fext, fhyp, (size_t)B * 6))) return rc2;
-    HIPCHK(hipStreamSynchronize(h->stream));
-    h->has_fext = true;
-    h->fext_frame = o.frame;
-    drop_graphs(h);  // captured graphs hold the old wrench kernel choice
-    // i7m_admm_reset of the rows [lo, lo + n), asynchronous on stream s
-    auto admm_reset_rows = [&](long lo, int n, int what, hipStream_t s) -> int {
-      const long m = 12L * N;
-      const AdmmArgs a = admm_layout(h->d_admm, h->d_admm_it, h->cfg.max_batch, N, lo);
-      if (what & I7M_ADMM_RESET_PRIMAL) {
-        HIPCHK(hipMemsetAsync(a.sx, 0, (size_t)n * T * 8, s));
-        HIPCHK(hipMemsetAsync(a.sz, 0, (size_t)n * m * 8, s));
-        HIPCHK(hipMemsetAsync(a.sq, 0, (size_t)n * T * 8, s));
-      }
-      if (what & I7M_ADMM_RESET_DUAL) HIPCHK(hipMemsetAsync(a.sy, 0, (size_t)n * m * 8, s));
-      if (what & I7M_ADMM_RESET_RHO)
-        HIPCHK(hipMemcpyAsync(a.srho, d_rho0 + lo, (size_t)n * 8, hipMemcpyDeviceToDevice, s));
-      return I7M_OK;
+  size_t bytes[SAMPLED_WS_COUNT];
+  sampled_ws_bytes(G, H, N, num_steps, n_endpoints, o.n_actual, noise != nullptr, bytes);
+  // host staging, declared first: alive until the workspace's final synchronize
+  const LoopStart start(h, B, G, endpoints);
+  std::vector<double> xrows((size_t)B * 12), rho0((size_t)B, h->cfg.admm_rho);
+  Workspace ws(h, bytes);
+  if (!ws.base) return fail(I7M_ENOMEM, "mpc_run_sampled: device allocation failed");
+  double *d_ep = ws.at<double>(SWS_EP), *d_xcur = ws.at<double>(SWS_XCUR), *d_xub = ws.at<double>(SWS_XUB),
+         *d_fact = ws.at<double>(SWS_FACT), *d_noise = bytes[SWS_NOISE] ? ws.at<double>(SWS_NOISE) : nullptr,
+         *d_dist = ws.at<double>(SWS_DIST), *d_q = ws.at<double>(SWS_Q), *d_fb = ws.at<double>(SWS_FB),
+         *d_rho0 = ws.at<double>(SWS_RHO0);
+  int *d_best = ws.at<int>(SWS_BEST), *d_gi = ws.at<int>(SWS_GI), *d_alive = ws.at<int>(SWS_ALIVE),
+      *d_bh = ws.at<int>(SWS_BH);
+  const size_t hist = history_rows(num_steps, G);
+  // src/gato_mpc_batch_sample.py:111-128: goal = endpoint 0 tiled, XU = [xstart, 0...], every
+  // row of a group at the group's start state, the hypotheses set on the solver
+  for (size_t b = 0; b < (size_t)B; ++b)
+    for (int r = 0; r < 12; ++r) xrows[b * 12 + r] = xstart[(b / H) * 12 + r];
+  int rc;
+  if ((rc = copy_in(h, h->d_xs, xrows.data(), xrows.size()))) return rc;
+  if ((rc = copy_in(h, d_xcur, xstart, (size_t)G * 12))) return rc;
+  if ((rc = loop_start(h, start, endpoints, n_endpoints, d_ep, d_gi, d_alive))) return rc;
+  if ((rc = copy_in(h, d_fact, f_actual, 6 * (size_t)o.n_actual * G))) return rc;
+  if (d_noise && (rc = copy_in(h, d_noise, noise, 3 * (size_t)num_steps * B))) return rc;
+  if ((rc = copy_in(h, d_rho0, rho0.data(), rho0.size()))) return rc;
+  HIPCHK(hipMemcpy2DAsync(h->d_xu, T * 8, xrows.data(), 12 * 8, 12 * 8, (size_t)B, hipMemcpyHostToDevice, h->stream));
+  HIPCHK(hipMemsetAsync(d_best, 0, 4 * (size_t)G, h->stream));  // the initial solve's XU_best is row 0, :128
+  HIPCHK(hipMemsetAsync(h->d_fext, 0, (size_t)h->cfg.max_batch * 6 * 8, h->stream));
+  if ((rc = copy_in(h, h->d_fext, fhyp, (size_t)B * 6))) return rc;
+  HIPCHK(hipStreamSynchronize(h->stream));
+  h->has_fext = true;
+  h->fext_frame = o.frame;
+  drop_graphs(h);  // captured graphs hold the old wrench kernel choice
+  // the rows [lo, lo + n) (whole groups) through every MPC step on stream s, as i7m_mpc_run's
+  // ranges: the groups are independent, so a staggered range runs its steps on its own
+  rc = run_ranges(h, B, [&](long lo, int n, hipStream_t s, StaggerMark* mark) -> int {
+    const long glo = lo / H;
+    const int ng = n / H;
+    double *xu = h->d_xu + lo * T, *out = h->d_out + lo * T, *xs = h->d_xs + lo * 12, *g = h->d_goal + lo * 3 * N;
+    // the solver state of these rows afresh, asynchronous on s (ADMM mode)
+    auto reset = [&](int what) {
+      return admm && what ? admm_reset_rows(h, lo, n, what, s, d_rho0 + lo, hipMemcpyDeviceToDevice) : I7M_OK;
     };
-    // the rows [lo, lo + n) (whole groups) through every MPC step on stream s, as i7m_mpc_run's
-    // ranges: the groups are independent, so a staggered range runs its steps on its own
-    auto loop = [&](long lo, int n, hipStream_t s, StaggerMark* mark) -> int {
-      const long glo = lo / H;
-      const int ng = n / H;
-      double *xu = h->d_xu + lo * T, *out = h->d_out + lo * T, *xs = h->d_xs + lo * 12, *g = h->d_goal + lo * 3 * N;
-      SampledArgs a{};
-      a.N = N;
-      a.H = H;
-      a.n_endpoints = n_endpoints;
-      a.frame_world = o.frame == I7M_WRENCH_WORLD;
-      a.keep_best = o.keep_best != 0;
-      a.sim_dt = o.sim_dt;
-      a.decay = o.decay;
-      a.xs = xs;
-      a.XU = xu;
-      a.xu_new = out;
-      a.goals = g;
-      a.fext = h->d_fext + lo * 6;
-      a.xcur = d_xcur + glo * 12;
-      a.xub = d_xub + glo * T;
-      a.best = d_best + glo;
-      a.goal_idx = d_gi + glo;
-      a.alive = d_alive + glo;
-      a.endpoints = d_ep;
-      int rc3;
-      if (admm && (rc3 = admm_reset_rows(lo, n, I7M_ADMM_RESET_ALL, s))) return rc3;  // solver state afresh
-      if ((rc3 = run_sqp(h, n, xu, out, xs, g, 3, h->d_stats + lo, lo, s, mark))) return rc3;
-      // launch i: select(i - 1) (i = 0: the initial solve's row 0), then plant(i) ... goal(i);
-      // the last launch only selects
-      for (int i = 0; i <= num_steps; ++i) {
-        a.select = i == 0 ? 2 : 1;
-        a.plant = i < num_steps;
-        const size_t rec = ((size_t)std::max(i - 1, 0)) * G + glo, cur = (size_t)std::min(i, std::max(num_steps - 1, 0)) * G + glo;
-        a.noise = d_noise && i > 0 ? d_noise + ((size_t)(i - 1) * B + lo) * 3 : nullptr;
-        a.best_out = d_bh + rec;
-        a.fbest_out = d_fb + rec * 6;
-        a.f_actual = d_fact + ((size_t)(o.n_actual > 1 ? std::min(i, o.n_actual - 1) : 0) * G + glo) * 6;
-        a.dist_out = d_dist + cur;
-        a.q_out = d_q + cur * 6;
-        hipLaunchKernelGGL(k_sampled_step, dim3(ng), dim3((H + 63) / 64 * 64), 0, s, h->d_model, a);
-        HIPCHK(hipGetLastError());
-        if (!a.plant) break;
-        if (admm && o.reset_what && (rc3 = admm_reset_rows(lo, n, o.reset_what, s))) return rc3;
-        if ((rc3 = run_sqp(h, n, xu, out, xs, g, 3, h->d_stats + lo, lo, s))) return rc3;
-      }
-      return I7M_OK;
-    };
-    if (stagger_applies(h->tune, h->cfg.qp_mode, B)) {
-      if ((rc2 = run_staggered(h, B, loop, stagger_cut_grouped(B, H)))) return rc2;
-    } else if ((rc2 = loop(0, B, h->stream, nullptr))) {
-      return rc2;
+    SampledArgs a{};
+    a.N = N;
+    a.H = H;
+    a.n_endpoints = n_endpoints;
+    a.frame_world = o.frame == I7M_WRENCH_WORLD;
+    a.keep_best = o.keep_best != 0;
+    a.sim_dt = o.sim_dt;
+    a.decay = o.decay;
+    a.xs = xs;
+    a.XU = xu;
+    a.xu_new = out;
+    a.goals = g;
+    a.fext = h->d_fext + lo * 6;
+    a.xcur = d_xcur + glo * 12;
+    a.xub = d_xub + glo * T;
+    a.best = d_best + glo;
+    a.goal_idx = d_gi + glo;
+    a.alive = d_alive + glo;
+    a.endpoints = d_ep;
+    int rc3;
+    if ((rc3 = reset(I7M_ADMM_RESET_ALL))) return rc3;
+    if ((rc3 = run_sqp(h, n, xu, out, xs, g, 3, nullptr, lo, s, mark))) return rc3;
+    // launch i: select(i - 1) (i = 0: the initial solve's row 0), then plant(i) ... goal(i);
+    // the last launch only selects
+    for (int i = 0; i <= num_steps; ++i) {
+      a.select = i == 0 ? 2 : 1;
+      a.plant = i < num_steps;
+      const size_t rec = ((size_t)std::max(i - 1, 0)) * G + glo, cur = (size_t)std::min(i, std::max(num_steps - 1, 0)) * G + glo;
+      a.noise = d_noise && i > 0 ? d_noise + ((size_t)(i - 1) * B + lo) * 3 : nullptr;
+      a.best_out = d_bh + rec;
+      a.fbest_out = d_fb + rec * 6;
+      a.f_actual = d_fact + ((size_t)(o.n_actual > 1 ? std::min(i, o.n_actual - 1) : 0) * G + glo) * 6;
+      a.dist_out = d_dist + cur;
+      a.q_out = d_q + cur * 6;
+      hipLaunchKernelGGL(k_sampled_step, dim3(ng), dim3((H + 63) / 64 * 64), 0, s, h->d_model, a);
+      HIPCHK(hipGetLastError());
+      if (!a.plant) break;
+      if ((rc3 = reset(o.reset_what))) return rc3;
+      if ((rc3 = run_sqp(h, n, xu, out, xs, g, 3, nullptr, lo, s))) return rc3;
     }
-    if (num_steps > 0) {
-      if ((rc2 = copy_out(h, dist_out, d_dist, hist))) return rc2;
-      if (q_out && (rc2 = copy_out(h, q_out, d_q, hist * 6))) return rc2;
-      if (fbest_out && (rc2 = copy_out(h, fbest_out, d_fb, hist * 6))) return rc2;
-      if (best_out) HIPCHK(hipMemcpyAsync(best_out, d_bh, 4 * hist, hipMemcpyDeviceToHost, h->stream));
-    }
-    if (xcur_out && (rc2 = copy_out(h, xcur_out, d_xcur, (size_t)G * 12))) return rc2;
-    if (xu_best_out && (rc2 = copy_out(h, xu_best_out, d_xub, (size_t)G * T))) return rc2;
-    if (fhyp_out && (rc2 = copy_out(h, fhyp_out, h->d_fext, (size_t)B * 6))) return rc2;
-    HIPCHK(hipStreamSynchronize(h->stream));
     return I7M_OK;
-  };
-  const int rc = run();
-  (void)hipStreamSynchronize(h->stream);
-  cleanup();
-  return rc;
+  }, stagger_cut_grouped(B, H));
+  if (rc) return rc;
+  if (num_steps > 0) {
+    if ((rc = copy_out(h, dist_out, d_dist, hist))) return rc;
+    if (q_out && (rc = copy_out(h, q_out, d_q, hist * 6))) return rc;
+    if (fbest_out && (rc = copy_out(h, fbest_out, d_fb, hist * 6))) return rc;
+    if (best_out) HIPCHK(hipMemcpyAsync(best_out, d_bh, 4 * hist, hipMemcpyDeviceToHost, h->stream));
+  }
+  if (xcur_out && (rc = copy_out(h, xcur_out, d_xcur, (size_t)G * 12))) return rc;
+  if (xu_best_out && (rc = copy_out(h, xu_best_out, d_xub, (size_t)G * T))) return rc;
+  if (fhyp_out && (rc = copy_out(h, fhyp_out, h->d_fext, (size_t)B * 6))) return rc;
+  return i7m_synchronize(h);
 }
 
 int i7m_set_timing(i7m_handle* h, int enable) {

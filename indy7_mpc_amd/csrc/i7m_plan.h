@@ -1,7 +1,7 @@
 // i7m_plan.h — the launch plan of libindy7mpc.so as pure host code: which kernel variant a launch
-// of a given size runs, whether a batch staggers, where its ranges and chunks begin.  No HIP here
-// (tests/host/plan_check.cpp compiles it with a plain C++17 compiler); i7m_api.hip asks these
-// selectors and only launches.
+// of a given size runs, whether a batch staggers, where its ranges and chunks begin, and how a
+// closed loop's per-call workspace is carved.  No HIP here (tests/host/plan_check.cpp compiles it
+// with a plain C++17 compiler); i7m_api.hip asks these selectors and only launches.
 #pragma once
 
 #include <algorithm>
@@ -201,7 +201,7 @@ inline int h2h_chunks_for(const Tuning& t, int qp_mode, int B) {
   int n;
   if (t.h2h_chunks > 0) n = t.h2h_chunks;
   // ADMM mode where the device solve staggers: two chunks, the second's solve behind the first's
-  // mark (solve_h2h_pipelined_body), i.e. the staggered halves with the copies overlapped
+  // mark (solve_h2h_pipelined), i.e. the staggered halves with the copies overlapped
   else if (stagger_applies(t, qp_mode, B)) n = 2;
   else n = B >= H2H_3_MIN_B ? 3 : (B >= H2H_2_MIN_B ? 2 : 1);
   return std::min(n, B);
@@ -214,6 +214,50 @@ inline long chunk_lo(int B, int nch, int i, bool taper) {
   if (i == 0) return 0;
   if (i == nch) return B;
   return (long)((double)B * (2 * i - 1) / (2.0 * (nch - 1)));
+}
+
+// ---- the per-call workspace of the closed loops ---------------------------------------------------
+
+// n sub-buffers of bytes[i] bytes carved from one allocation: off[i] is where sub-buffer i begins,
+// a multiple of WS_ALIGN; returns the size of the allocation.  A zero-sized request takes no room.
+constexpr size_t WS_ALIGN = 256;
+inline size_t carve(const size_t* bytes, int n, size_t* off) {
+  size_t total = 0;
+  for (int i = 0; i < n; ++i) {
+    off[i] = total;
+    total += (bytes[i] + WS_ALIGN - 1) / WS_ALIGN * WS_ALIGN;
+  }
+  return total;
+}
+// rows of a closed loop's per-step histories (one row even for a run of 0 steps)
+inline size_t history_rows(int num_steps, int instances) { return (size_t)std::max(num_steps, 1) * instances; }
+// i7m_mpc_run's request: the endpoints, the distance and q histories, goal index and alive flag per instance
+enum { MPC_WS_EP, MPC_WS_DIST, MPC_WS_Q, MPC_WS_GI, MPC_WS_ALIVE, MPC_WS_COUNT };
+inline void mpc_ws_bytes(int B, int n_endpoints, int num_steps, size_t bytes[MPC_WS_COUNT]) {
+  const size_t hist = history_rows(num_steps, B);
+  bytes[MPC_WS_EP] = 3 * 8 * (size_t)n_endpoints;
+  bytes[MPC_WS_DIST] = 8 * hist;
+  bytes[MPC_WS_Q] = 6 * 8 * hist;
+  bytes[MPC_WS_GI] = bytes[MPC_WS_ALIVE] = 4 * (size_t)B;
+}
+// i7m_mpc_run_sampled's, G groups of H rows: the endpoints; per group the state, XU_best, the actual
+// wrench schedule; the noise schedule; the distance, q and winning-wrench histories; the rows' rho;
+// per group the winner, goal index and alive flag; the winners' history
+enum { SWS_EP, SWS_XCUR, SWS_XUB, SWS_FACT, SWS_NOISE, SWS_DIST, SWS_Q, SWS_FB, SWS_RHO0, SWS_BEST, SWS_GI, SWS_ALIVE,
+       SWS_BH, SAMPLED_WS_COUNT };
+inline void sampled_ws_bytes(int G, int H, int N, int num_steps, int n_endpoints, int n_actual, bool noise,
+                             size_t bytes[SAMPLED_WS_COUNT]) {
+  const size_t hist = history_rows(num_steps, G), B = (size_t)G * H;
+  bytes[SWS_EP] = 3 * 8 * (size_t)n_endpoints;
+  bytes[SWS_XCUR] = 12 * 8 * (size_t)G;
+  bytes[SWS_XUB] = 8 * (18 * (size_t)N - 6) * G;
+  bytes[SWS_FACT] = 6 * 8 * (size_t)n_actual * G;
+  bytes[SWS_NOISE] = noise ? 3 * 8 * (size_t)num_steps * B : 0;
+  bytes[SWS_DIST] = 8 * hist;
+  bytes[SWS_Q] = bytes[SWS_FB] = 6 * 8 * hist;
+  bytes[SWS_RHO0] = 8 * B;
+  bytes[SWS_BEST] = bytes[SWS_GI] = bytes[SWS_ALIVE] = 4 * (size_t)G;
+  bytes[SWS_BH] = 4 * hist;
 }
 
 }  // namespace i7m

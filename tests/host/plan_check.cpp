@@ -1,7 +1,8 @@
 // plan_check.cpp — the launch plan (indy7_mpc_amd/csrc/i7m_plan.h) checked on the host: range and
-// chunk coverage, the pinned size thresholds, and the retired environment variables.  A
-// stand-alone program (tests/test_plan_host.py builds it with the host compiler under
-// -fsanitize=address,undefined and runs it); prints every failed check, exit status 1 on any.
+// chunk coverage, the pinned size thresholds, the retired environment variables, and the closed
+// loops' workspace carve.  A stand-alone program (tests/test_plan_host.py builds it with the host
+// compiler under -fsanitize=address,undefined and runs it); prints every failed check, exit status
+// 1 on any.
 #include <cstdio>
 #include <cstdlib>
 #include <string>
@@ -145,10 +146,43 @@ static void environment() {
   CHECK(!tuning_from_env(cfg, &t, &err) && err.find("h2h_chunks") != std::string::npos, "h2h_chunks = 65 accepted");
 }
 
+// carve: every offset a multiple of 256, no two sub-buffers overlapping, the total covering the last
+static void check_carve(const std::vector<size_t>& bytes, const char* what) {
+  std::vector<size_t> off(bytes.size(), ~(size_t)0);
+  const size_t total = carve(bytes.data(), (int)bytes.size(), off.data());
+  for (size_t i = 0; i < bytes.size(); ++i) {
+    CHECK(off[i] % 256 == 0, "%s: offset %zu = %zu", what, i, off[i]);
+    CHECK(off[i] + bytes[i] <= total, "%s: sub-buffer %zu [%zu, +%zu) past the total %zu", what, i, off[i], bytes[i], total);
+    for (size_t j = 0; j < i; ++j)
+      CHECK(off[j] + bytes[j] <= off[i] || off[i] + bytes[i] <= off[j], "%s: sub-buffers %zu and %zu overlap", what, j, i);
+  }
+}
+
+static void workspace() {
+  check_carve({}, "no request");
+  check_carve({0}, "one empty request");
+  check_carve({0, 1, 0, 255, 256, 257, 0}, "sizes around the alignment");
+  // the sampled loop's 13 sub-buffers at (G, H, N, steps): the smallest call, and the timed shape
+  const int shapes[2][4] = {{1, 1, 2, 0}, {256, 16, 32, 20}};
+  for (const auto& s : shapes)
+    for (int noise = 0; noise < 2; ++noise) {
+      size_t bytes[SAMPLED_WS_COUNT];
+      sampled_ws_bytes(s[0], s[1], s[2], s[3], 2, 1, noise != 0, bytes);
+      CHECK(SAMPLED_WS_COUNT == 13, "sampled request has %d sub-buffers", (int)SAMPLED_WS_COUNT);
+      CHECK((bytes[SWS_NOISE] == 0) == (noise == 0 || s[3] == 0), "noise bytes %zu", bytes[SWS_NOISE]);
+      CHECK(bytes[SWS_DIST] >= 8 * (size_t)s[0], "a run of 0 steps still has one history row");
+      check_carve(std::vector<size_t>(bytes, bytes + SAMPLED_WS_COUNT), "sampled loop");
+    }
+  size_t bytes[MPC_WS_COUNT];
+  mpc_ws_bytes(3, 2, 0, bytes);
+  check_carve(std::vector<size_t>(bytes, bytes + MPC_WS_COUNT), "mpc_run");
+}
+
 int main() {
   coverage();
   pinned();
   environment();
+  workspace();
   if (g_failed) {
     std::printf("%d check(s) failed\n", g_failed);
     return 1;

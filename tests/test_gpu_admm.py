@@ -465,3 +465,25 @@ def test_admm_prep_variants_bit_identical(lib, model, monkeypatch, B, N):
         h.close()
     for a, b in zip(res[0], res[1]):
         np.testing.assert_array_equal(a, b)
+
+
+def test_admm_partial_reset_leaves_the_other_rows(lib, model):
+    """admm_reset(B=2) on a handle that carries six problems' state: rows 0-1 are a fresh solver's
+    (x, z, y, q zero, rho the configured one, the iteration and status records -1), rows 2-5 of all
+    seven arrays keep their values bit for bit."""
+    N, B = 8, 6
+    xcur, goals, XU = synthetic_batch(B, N, 52)
+    h = lib.Handle(model, N=N, max_batch=B, qp_mode=lib.QP_ADMM)
+    first, _ = h.solve(xcur, goals, XU)
+    h.solve(xcur, goals, first)
+    before = list(h.admm_state(B)) + [h.admm_stats(B, with_status=True)[i] for i in (0, 2)]
+    assert all(a[:2].any() for a in before[:4]) and (before[5][:, 0] > 0).all()
+    h.admm_reset(B=2, what=lib.ADMM_RESET_ALL)
+    after = list(h.admm_state(B)) + [h.admm_stats(B, with_status=True)[i] for i in (0, 2)]
+    for name, a in zip("xzyq", after[:4]):
+        assert not a[:2].any(), name
+    np.testing.assert_array_equal(after[4][:2], np.full(2, lib.ADMM_DEFAULTS["rho"]))
+    for a in after[5:]:
+        np.testing.assert_array_equal(a[:2], np.full((2, lib.MAX_SQP), -1))
+    for name, a, b in zip(("x", "z", "y", "q", "rho", "iters", "status"), after, before):
+        np.testing.assert_array_equal(a[2:], b[2:], err_msg=name)

@@ -383,3 +383,24 @@ def test_split_line_search_bit_identical(lib, model, monkeypatch, tail):
     st = outs["0"][0][1]
     used = np.arange(st["alphas"].shape[1])[None, :] < st["n_alphas"][:, None]
     assert (used & (st["alphas"] < 0.5 ** (2 * int(tail) - 1))).any()
+
+
+def test_query_hooks_past_one_chunk(lib, model):
+    """A max_batch = 1, N = 8 handle's scratch holds 810 queries (256 for aba_derivatives): 1627 rows
+    (519) are two full chunks plus 7 rows.  Every output equals, bit for bit, that of a
+    max_batch = 512 handle, which serves each call in one chunk."""
+    n, nd = 1627, 519
+    rng = np.random.default_rng(77)
+    q, v, u = rng.uniform(-1, 1, (n, 6)), rng.uniform(-0.5, 0.5, (n, 6)), rng.uniform(-5, 5, (n, 6))
+    f = rng.normal(0, 5.0, (n, 6))
+    small, big = lib.Handle(model, N=8, max_batch=1), lib.Handle(model, N=8, max_batch=512)
+
+    def calls(h):
+        p, J = h.eepos(q, jacobian=True)
+        return [p, J, h.aba(q, v, u, fext=f, frame="world"), *h.rk4(q, v, u, 0.01, fext=f, frame="world"),
+                *h.aba_derivatives(q[:nd], v[:nd], u[:nd])]
+
+    names = ("eepos p", "eepos J", "aba", "rk4 q", "rk4 v", "abad dq", "abad dv", "abad Minv", "abad a")
+    for name, a, b in zip(names, calls(small), calls(big)):
+        assert np.isfinite(b).all(), name
+        np.testing.assert_array_equal(a, b, err_msg=name)

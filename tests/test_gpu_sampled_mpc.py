@@ -281,3 +281,37 @@ def test_drop_in_class_names_the_true_hypothesis(lib, model):
     assert len(stats["goal_distances"]) == 2  # logged every 0.05 s: steps 0 and 5
     np.testing.assert_array_equal(stats["best_ids"], np.full(6, 2))
     np.testing.assert_array_equal(stats["f_ext_best"], np.tile(f, (6, 1)))
+
+
+def test_repeated_closed_loop_calls_on_one_handle(lib, model):
+    """One handle serves mpc_run and mpc_run_sampled calls of different shapes in turn: a repeated
+    call returns the same arrays bit for bit, whatever ran between (per-call device state does not
+    leak from one call into the next)."""
+    N, steps = 8, 3
+    h = _handle(lib, model, N, 8, "direct")
+    xs3, ends, _, _, _ = make_case(3, 2, seed=1)
+    plain = h.mpc_run(xs3, ends, 4)
+    for a, b in zip(h.mpc_run(xs3, ends, 4), plain):
+        np.testing.assert_array_equal(a, b)
+
+    def sampled(hh, G, H, **kw):
+        xs, _, fhyp, fact, _ = make_case(G, H, seed=8)
+        noise = np.random.default_rng(9).normal(0, 2.0, (steps, G * H, 3))
+        return hh.mpc_run_sampled(xs, ends, steps, fhyp, fact, noise=noise, sim_dt=0.01, **kw)
+
+    first = sampled(h, 2, 4)
+    sampled(h, 1, 8)
+    third = sampled(h, 2, 4)
+    assert np.isfinite(first["dist"]).all()
+    for key in first:
+        np.testing.assert_array_equal(third[key], first[key], err_msg=key)
+    with pytest.raises(lib.I7MError, match="external wrench"):
+        h.mpc_run(xs3, ends, 4)
+    h.set_external_wrench(None)
+    for a, b in zip(h.mpc_run(xs3, ends, 4), plain):
+        np.testing.assert_array_equal(a, b)
+    ha = _handle(lib, model, N, 8, "admm")
+    one = sampled(ha, 2, 4, reset_what=lib.ADMM_RESET_ALL)
+    two = sampled(ha, 2, 4, reset_what=lib.ADMM_RESET_ALL)
+    for key in one:
+        np.testing.assert_array_equal(two[key], one[key], err_msg=key)
