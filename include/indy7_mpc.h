@@ -38,6 +38,8 @@
  *   i7m_mpc_run_sampled        MPC_GATO_Batch_Sample.run_mpc over G controllers of H wrench
  *                              hypotheses       src/gato_mpc_batch_sample.py:106-300
  *                              (find_best_idx / resample_f_ext_batch, gato_controller.py:109-129)
+ *   i7m_mpc_run_tracking       GATO_Controller.joint_callback: that loop tracking a reference
+ *                              trajectory                     gato_controller.py:201-250
  *
  * Layouts (all fp64, C-contiguous, row = problem):
  *   XU    (B, T)  T = 18N-6, [x_0,u_0,x_1,u_1,...,x_{N-1}], x=[q(6),v(6)]  src/osqp_solver.py:22
@@ -79,7 +81,8 @@ extern "C" {
 #define I7M_MAX_N 64
 
 /* ABI revision, returned by i7m_abi_version(); bumped whenever an existing signature, struct
- * layout, field meaning or enum count changes.  6: i7m_get_admm_status has the value 2 ("solved
+ * layout, field meaning or enum count changes.  7: i7m_mpc_run_tracking (appended; nothing
+ * existing changed) (0.7 builds).  6: i7m_get_admm_status has the value 2 ("solved
  * inaccurate") and, after admm_max_iter, runs OSQP's closing tests (0.6 builds).  5: i7m_get_admm_status and i7m_get_admm_dual
  * (appended); i7m_get_admm_stats' iteration record is reset to -1 at the start of every solve
  * (0.5 builds).  4: I7M_QP_ADMM and i7m_config's admm_* fields
@@ -90,7 +93,7 @@ extern "C" {
  * 2: i7m_aba / i7m_rk4 take a wrench `frame` before their outputs and i7m_set_external_wrench a
  * trailing `frame` (0.2 builds); 1 had neither.  A caller built against another revision must not
  * call through this library: compare first. */
-#define I7M_ABI_VERSION 6
+#define I7M_ABI_VERSION 7
 
 #define I7M_OK 0
 #define I7M_EINVAL -1   /* bad argument (size, null pointer, unsupported N) */
@@ -373,6 +376,35 @@ int i7m_mpc_run_sampled(i7m_handle* h, int32_t G, int32_t H, const double* xstar
                         int32_t n_endpoints, int32_t num_steps, const double* fhyp, const double* f_actual,
                         const double* noise, const i7m_sampled_opts* opts, double* dist_out, int32_t* best_out,
                         double* q_out, double* fbest_out, double* xcur_out, double* xu_best_out, double* fhyp_out);
+
+/* The sampled-wrench closed loop tracking a reference trajectory: the deployed controller's loop
+ * (GATO_Controller.joint_callback, gato_controller.py:201-250) over G controllers of H hypotheses.  It is
+ * i7m_mpc_run_sampled (same options, same init / plant / spread / reset / solve / select / resample
+ * order, same staggered ranges, same wrench left on the handle) with the goal source replaced:
+ *   init    every row of group g is solved against the window at offset 0,
+ *           goals[k] = ref[min(ph_g + k, L - 1)][0:3], k = 0 .. N-1 (:180-183), ph_g = ref_phase[g]
+ *           or 0
+ *   step i, in the goal's place:
+ *     track    err_out[i, g] = |eepos(xcur q) - ref[min(ph_g + ref_offset[i], L - 1)]|, the tracking
+ *              error the controller logs against the window's first point (:242-246);
+ *              ee_out[i, g] = eepos(xcur q); then every row of g gets the window
+ *              goals[k] = ref[min(ph_g + ref_offset[i] + k, L - 1)][0:3] (:214-216).  A window that
+ *              runs past the end of the reference holds its last point (the controller's slice
+ *              would come up short there).  No radius test: a tracking group never stops.
+ * ref is (L, ref_stride), ref_stride 3 or 6 (the controller stores [x y z 0 0 0] per point; the
+ * first three are read).  ref_offset (num_steps) int32 is the caller's window schedule, like
+ * f_actual and noise; the controller's rule int(sum of elapsed / dt) is one.  ref_phase (G) int32
+ * may be NULL.  With L = 1 the loop is i7m_mpc_run_sampled's with that one endpoint, as long as
+ * that one does not reach it.
+ * Outputs as i7m_mpc_run_sampled's, err_out (num_steps, G) required, ee_out (num_steps, G, 3)
+ * optional.  Synchronous.  I7M_EINVAL before any work for i7m_mpc_run_sampled's refusals and for
+ * L < 1, ref_stride other than 3 or 6, a negative ref_offset or ref_phase entry, and null ref,
+ * ref_offset (with num_steps > 0) or err_out. */
+int i7m_mpc_run_tracking(i7m_handle* h, int32_t G, int32_t H, const double* xstart, const double* ref, int32_t L,
+                         int32_t ref_stride, const int32_t* ref_phase, const int32_t* ref_offset, int32_t num_steps,
+                         const double* fhyp, const double* f_actual, const double* noise, const i7m_sampled_opts* opts,
+                         double* err_out, int32_t* best_out, double* q_out, double* ee_out, double* fbest_out,
+                         double* xcur_out, double* xu_best_out, double* fhyp_out);
 
 /* Per-kernel device timing with HIP events on the launch stream. */
 enum { I7M_K_LIN = 0, I7M_K_RICCATI = 1, I7M_K_LINESEARCH = 2, I7M_K_RICCATI_BOX = 3, I7M_K_IPM = 4, I7M_K_IPM_FUSED = 5,

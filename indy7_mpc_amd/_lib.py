@@ -20,7 +20,7 @@ import numpy as np
 LIB_DIR = os.path.join(os.path.dirname(os.path.abspath(__file__)), "lib")
 LIB_PATH = os.environ.get("I7M_LIB", os.path.join(LIB_DIR, "libindy7mpc.so"))  # I7M_LIB: A/B builds
 
-ABI_VERSION = 6  # I7M_ABI_VERSION of include/indy7_mpc.h this binding's SIGNATURES follow
+ABI_VERSION = 7  # I7M_ABI_VERSION of include/indy7_mpc.h this binding's SIGNATURES follow
 NJ, NX, NU = 6, 12, 6
 MAX_SQP = 8
 MAX_N = 64
@@ -166,6 +166,9 @@ SIGNATURES = [
     ("i7m_sampled_opts_default", C.c_int, [C.POINTER(i7m_sampled_opts)]),
     ("i7m_mpc_run_sampled", C.c_int, [_H, C.c_int32, C.c_int32, _DP, _DP, C.c_int32, C.c_int32, _DP, _DP, _DP,
                                       C.POINTER(i7m_sampled_opts), _DP, _IP32, _DP, _DP, _DP, _DP, _DP]),
+    ("i7m_mpc_run_tracking", C.c_int, [_H, C.c_int32, C.c_int32, _DP, _DP, C.c_int32, C.c_int32, _IP32, _IP32, C.c_int32,
+                                       _DP, _DP, _DP, C.POINTER(i7m_sampled_opts), _DP, _IP32, _DP, _DP, _DP, _DP, _DP,
+                                       _DP]),
     ("i7m_set_timing", C.c_int, [_H, C.c_int]),
     ("i7m_get_kernel_times", C.c_int, [_H, _DP, C.POINTER(C.c_int32), C.c_int32]),
     ("i7m_reset_kernel_times", C.c_int, [_H]),
@@ -452,22 +455,15 @@ class Handle:
                                      _ptr(xc), _ptr(xu)))
         return d, q, xc, xu
 
-    def mpc_run_sampled(self, xstart, endpoints, num_steps, fhyp, f_actual, noise=None, sim_dt=0.001, frame="world",
-                        reset_what=ADMM_RESET_ALL, keep_best=False, decay=1.0):
-        """Sampled-wrench closed loop of G controllers with H hypotheses each on the device
-        (i7m_mpc_run_sampled): xstart (G, 12), endpoints (E, 3), fhyp (G * H, 6) with group g owning
-        rows [g H, (g + 1) H), f_actual (G, 6) held for the run or (num_steps, G, 6), noise
-        (num_steps, G * H, 3) or None (no resampling).  Returns a dict: dist (num_steps, G), best
-        (num_steps, G) int32, q and fbest (num_steps, G, 6), xcur (G, 12), xu_best (G, T), fhyp
-        (G * H, 6) the final hypotheses (also left set on the handle, in `frame`)."""
+    def _sampled_inputs(self, xstart, num_steps, fhyp, f_actual, noise, sim_dt, frame, reset_what, keep_best, decay):
+        """The arguments mpc_run_sampled and mpc_run_tracking share, as contiguous arrays and the
+        options struct: (xs, G, fh, H, fa, noise or None, opts)."""
         xs = _f64(xstart).reshape(-1, NX)
-        ep = _f64(endpoints).reshape(-1, 3)
         G = xs.shape[0]
         fh = _f64(fhyp).reshape(-1, 6)
         if G < 1 or fh.shape[0] % G:
             raise ValueError(f"fhyp has {fh.shape[0]} rows, not a multiple of the {G} groups")
         Hn = fh.shape[0] // G
-        num_steps = int(num_steps)
         fa = _f64(f_actual)
         if fa.size == G * 6:
             fa = fa.reshape(1, G, 6)
@@ -484,6 +480,20 @@ class Handle:
         _check(self._lib.i7m_sampled_opts_default(C.byref(o)))
         o.sim_dt, o.decay, o.frame = float(sim_dt), float(decay), _FRAMES[frame]
         o.reset_what, o.keep_best, o.n_actual = int(reset_what), int(bool(keep_best)), fa.shape[0]
+        return xs, G, fh, Hn, fa, nz, o
+
+    def mpc_run_sampled(self, xstart, endpoints, num_steps, fhyp, f_actual, noise=None, sim_dt=0.001, frame="world",
+                        reset_what=ADMM_RESET_ALL, keep_best=False, decay=1.0):
+        """Sampled-wrench closed loop of G controllers with H hypotheses each on the device
+        (i7m_mpc_run_sampled): xstart (G, 12), endpoints (E, 3), fhyp (G * H, 6) with group g owning
+        rows [g H, (g + 1) H), f_actual (G, 6) held for the run or (num_steps, G, 6), noise
+        (num_steps, G * H, 3) or None (no resampling).  Returns a dict: dist (num_steps, G), best
+        (num_steps, G) int32, q and fbest (num_steps, G, 6), xcur (G, 12), xu_best (G, T), fhyp
+        (G * H, 6) the final hypotheses (also left set on the handle, in `frame`)."""
+        ep = _f64(endpoints).reshape(-1, 3)
+        num_steps = int(num_steps)
+        xs, G, fh, Hn, fa, nz, o = self._sampled_inputs(xstart, num_steps, fhyp, f_actual, noise, sim_dt, frame,
+                                                         reset_what, keep_best, decay)
         out = dict(dist=np.empty((num_steps, G)), best=np.empty((num_steps, G), dtype=np.int32),
                    q=np.empty((num_steps, G, NJ)), fbest=np.empty((num_steps, G, 6)), xcur=np.empty((G, NX)),
                    xu_best=np.empty((G, self.T)), fhyp=np.empty((G * Hn, 6)))
@@ -492,6 +502,40 @@ class Handle:
                                              _ptr(out["dist"]), out["best"].ctypes.data_as(_IP32), _ptr(out["q"]),
                                              _ptr(out["fbest"]), _ptr(out["xcur"]), _ptr(out["xu_best"]),
                                              _ptr(out["fhyp"])))
+        return out
+
+    def mpc_run_tracking(self, xstart, ref, ref_offset, fhyp, f_actual, ref_phase=None, noise=None, sim_dt=0.01,
+                         frame="world", reset_what=ADMM_RESET_ALL, keep_best=False, decay=1.0):
+        """The sampled-wrench closed loop tracking a reference trajectory (i7m_mpc_run_tracking):
+        ref (L, 3) or (L, 6) (the first three of each point read), ref_offset (num_steps,) the
+        window's offset at every step, ref_phase (G,) the groups' start points on the reference or
+        None; the rest as mpc_run_sampled.  At step i every row of group g is solved against
+        ref[min(phase[g] + ref_offset[i] + k, L - 1)], k = 0 .. N-1.  Returns a dict: err
+        (num_steps, G) the distance of the EE to the window's first point, best, q, ee
+        (num_steps, G, 3), fbest, xcur, xu_best, fhyp."""
+        rf = _f64(ref)
+        if rf.ndim != 2:
+            raise ValueError("ref must be (L, 3) or (L, 6)")
+        L, stride = rf.shape
+        ro = np.ascontiguousarray(ref_offset, dtype=np.int32).reshape(-1)
+        num_steps = ro.shape[0]
+        xs, G, fh, Hn, fa, nz, o = self._sampled_inputs(xstart, num_steps, fhyp, f_actual, noise, sim_dt, frame,
+                                                         reset_what, keep_best, decay)
+        rp = None
+        if ref_phase is not None:
+            rp = np.ascontiguousarray(ref_phase, dtype=np.int32).reshape(-1)
+            if rp.shape[0] != G:
+                raise ValueError(f"ref_phase must be ({G},)")
+        out = dict(err=np.empty((num_steps, G)), best=np.empty((num_steps, G), dtype=np.int32),
+                   q=np.empty((num_steps, G, NJ)), ee=np.empty((num_steps, G, 3)), fbest=np.empty((num_steps, G, 6)),
+                   xcur=np.empty((G, NX)), xu_best=np.empty((G, self.T)), fhyp=np.empty((G * Hn, 6)))
+        _check(self._lib.i7m_mpc_run_tracking(self._h, G, Hn, _ptr(xs), _ptr(rf), L, stride,
+                                              rp.ctypes.data_as(_IP32) if rp is not None else None,
+                                              ro.ctypes.data_as(_IP32), num_steps, _ptr(fh), _ptr(fa),
+                                              _ptr(nz) if nz is not None else None, C.byref(o), _ptr(out["err"]),
+                                              out["best"].ctypes.data_as(_IP32), _ptr(out["q"]), _ptr(out["ee"]),
+                                              _ptr(out["fbest"]), _ptr(out["xcur"]), _ptr(out["xu_best"]),
+                                              _ptr(out["fhyp"])))
         return out
 
     # ---- timing --------------------------------------------------------------------------

@@ -993,6 +993,16 @@ struct LoopStart {
       : rows(rows_), goals(rows_ * 3 * h->N), ones(instances, 1) {
     for (size_t k = 0; k < goals.size(); ++k) goals[k] = endpoints[k % 3];
   }
+  // the tracking loop's start (gato_controller.py:180-183): every row of group g (H rows each) gets
+  // the reference's window at the group's phase and offset 0
+  LoopStart(const i7m_handle* h, size_t rows_, size_t instances, int H, const double* ref, long L, int ref_stride,
+            const int32_t* ref_phase)
+      : rows(rows_), goals(rows_ * 3 * h->N), ones(instances, 1) {
+    const size_t W = 3 * h->N;
+    for (size_t b = 0; b < rows; ++b)
+      for (size_t e = 0; e < W; ++e)
+        goals[b * W + e] = ref[track_index(ref_phase ? ref_phase[b / H] : 0, 0, (long)(e / 3), L) * ref_stride + e % 3];
+  }
 };
 int loop_start(i7m_handle* h, const LoopStart& st, const double* endpoints, int n_endpoints, double* d_ep, int* d_gi,
                int* d_alive) {
@@ -1602,60 +1612,100 @@ int i7m_sampled_opts_default(i7m_sampled_opts* o) {
   return I7M_OK;
 }
 
-int i7m_mpc_run_sampled(i7m_handle* h, int32_t G, int32_t H, const double* xstart, const double* endpoints,
-                        int32_t n_endpoints, int32_t num_steps, const double* fhyp, const double* f_actual,
-                        const double* noise, const i7m_sampled_opts* opts, double* dist_out, int32_t* best_out,
-                        double* q_out, double* fbest_out, double* xcur_out, double* xu_best_out, double* fhyp_out) {
+}  // extern "C"
+
+namespace {
+
+// The goal source of the sampled loop: the endpoints (i7m_mpc_run_sampled) or, with ref set, a
+// reference trajectory and the caller's window schedule (i7m_mpc_run_tracking).
+struct GoalSource {
+  const double* endpoints = nullptr;  // (n_endpoints, 3)
+  int n_endpoints = 0;
+  const double* ref = nullptr;  // (L, ref_stride)
+  long L = 0;
+  int ref_stride = 0;
+  const int32_t* ref_phase = nullptr;   // (G) or null
+  const int32_t* ref_offset = nullptr;  // (num_steps)
+};
+
+// The sampled-wrench closed loop of both entry points (`who` names the one in the messages).
+// ee_out: the tracking mode's EE history, null in endpoint mode.
+int sampled_loop(i7m_handle* h, const std::string& who, bool track, int32_t G, int32_t H, const double* xstart,
+                 const GoalSource& gs, int32_t num_steps, const double* fhyp, const double* f_actual, const double* noise,
+                 const i7m_sampled_opts* opts, double* dist_out, int32_t* best_out, double* q_out, double* ee_out,
+                 double* fbest_out, double* xcur_out, double* xu_best_out, double* fhyp_out) {
   if (!h) return fail(I7M_EINVAL, "null handle");
   i7m_sampled_opts o;
   (void)i7m_sampled_opts_default(&o);
   if (opts) o = *opts;
   if (h->cfg.qp_mode == I7M_QP_BOX)
-    return fail(I7M_EINVAL, "mpc_run_sampled: I7M_QP_BOX is not supported (I7M_QP_DIRECT or I7M_QP_ADMM)");
+    return fail(I7M_EINVAL, who + ": I7M_QP_BOX is not supported (I7M_QP_DIRECT or I7M_QP_ADMM)");
   if (H < 1 || H > 256 || (H & (H - 1)))
-    return fail(I7M_EINVAL, "mpc_run_sampled: H = " + std::to_string(H) + " is not one of 1, 2, 4, ..., 256");
+    return fail(I7M_EINVAL, who + ": H = " + std::to_string(H) + " is not one of 1, 2, 4, ..., 256");
   if (G < 0 || (long)G * H > h->cfg.max_batch)
-    return fail(I7M_EINVAL, "mpc_run_sampled: G x H = " + std::to_string((long)G * H) + " rows outside [0, max_batch=" +
+    return fail(I7M_EINVAL, who + ": G x H = " + std::to_string((long)G * H) + " rows outside [0, max_batch=" +
                                 std::to_string(h->cfg.max_batch) + "]");
-  if (!(o.sim_dt > 0.0) || !(o.sim_dt <= h->cfg.dt))
-    return fail(I7M_EINVAL, "mpc_run_sampled: sim_dt must be in (0, dt]");
+  if (!(o.sim_dt > 0.0) || !(o.sim_dt <= h->cfg.dt)) return fail(I7M_EINVAL, who + ": sim_dt must be in (0, dt]");
   if (o.frame != I7M_WRENCH_LOCAL && o.frame != I7M_WRENCH_WORLD)
-    return fail(I7M_EINVAL, "mpc_run_sampled: frame must be I7M_WRENCH_LOCAL or I7M_WRENCH_WORLD");
-  if (o.reset_what & ~I7M_ADMM_RESET_ALL) return fail(I7M_EINVAL, "mpc_run_sampled: unknown I7M_ADMM_RESET_* bits");
-  if (n_endpoints < 1 || num_steps < 0) return fail(I7M_EINVAL, "mpc_run_sampled: need >= 1 endpoint, num_steps >= 0");
-  if (o.n_actual != 1 && o.n_actual != num_steps)
-    return fail(I7M_EINVAL, "mpc_run_sampled: n_actual must be 1 or num_steps");
-  if (!xstart || !endpoints || !fhyp || !f_actual || !dist_out)
-    return fail(I7M_EINVAL, "mpc_run_sampled: null xstart, endpoints, fhyp, f_actual or dist_out");
+    return fail(I7M_EINVAL, who + ": frame must be I7M_WRENCH_LOCAL or I7M_WRENCH_WORLD");
+  if (o.reset_what & ~I7M_ADMM_RESET_ALL) return fail(I7M_EINVAL, who + ": unknown I7M_ADMM_RESET_* bits");
+  if (!track) {
+    if (gs.n_endpoints < 1 || num_steps < 0) return fail(I7M_EINVAL, who + ": need >= 1 endpoint, num_steps >= 0");
+  } else {
+    if (num_steps < 0) return fail(I7M_EINVAL, who + ": need num_steps >= 0");
+    if (gs.L < 1) return fail(I7M_EINVAL, who + ": L = " + std::to_string(gs.L) + ", the reference needs >= 1 point");
+    if (gs.ref_stride != 3 && gs.ref_stride != 6)
+      return fail(I7M_EINVAL, who + ": ref_stride = " + std::to_string(gs.ref_stride) + " is not 3 or 6");
+  }
+  if (o.n_actual != 1 && o.n_actual != num_steps) return fail(I7M_EINVAL, who + ": n_actual must be 1 or num_steps");
+  if (!track) {
+    if (!xstart || !gs.endpoints || !fhyp || !f_actual || !dist_out)
+      return fail(I7M_EINVAL, who + ": null xstart, endpoints, fhyp, f_actual or dist_out");
+  } else {
+    if (!xstart || !gs.ref || !fhyp || !f_actual || !dist_out)
+      return fail(I7M_EINVAL, who + ": null xstart, ref, fhyp, f_actual or err_out");
+    if (num_steps > 0 && !gs.ref_offset) return fail(I7M_EINVAL, who + ": null ref_offset with num_steps > 0");
+    const char* which = "";
+    int at = 0;
+    if (!track_schedule_ok(gs.ref_phase, G, gs.ref_offset, num_steps, &which, &at))
+      return fail(I7M_EINVAL, who + ": " + which + "[" + std::to_string(at) + "] is negative");
+  }
   if (G == 0) return I7M_OK;
   HIPCHK(hipSetDevice(h->dev));
   const int N = (int)h->N, B = G * H;
   const size_t T = h->T;
   const bool admm = h->cfg.qp_mode == I7M_QP_ADMM;
   // per-run state beyond the handle's buffers: per group the state, XU_best, the scored
-  // hypothesis, goal index and alive flag; the schedules and the histories
-  size_t bytes[SAMPLED_WS_COUNT];
-  sampled_ws_bytes(G, H, N, num_steps, n_endpoints, o.n_actual, noise != nullptr, bytes);
+  // hypothesis, goal index and alive flag; the schedules and the histories; the tracking mode's
+  // reference, phases and EE history
+  size_t bytes[TRACKING_WS_COUNT];
+  tracking_ws_bytes(G, H, N, num_steps, gs.n_endpoints, o.n_actual, noise != nullptr, gs.L, gs.ref_stride,
+                    gs.ref_phase != nullptr, bytes);
   // host staging, declared first: alive until the workspace's final synchronize
-  const LoopStart start(h, B, G, endpoints);
+  const LoopStart start = track ? LoopStart(h, B, G, H, gs.ref, gs.L, gs.ref_stride, gs.ref_phase)
+                                : LoopStart(h, B, G, gs.endpoints);
   std::vector<double> xrows((size_t)B * 12), rho0((size_t)B, h->cfg.admm_rho);
   Workspace ws(h, bytes);
-  if (!ws.base) return fail(I7M_ENOMEM, "mpc_run_sampled: device allocation failed");
+  if (!ws.base) return fail(I7M_ENOMEM, who + ": device allocation failed");
   double *d_ep = ws.at<double>(SWS_EP), *d_xcur = ws.at<double>(SWS_XCUR), *d_xub = ws.at<double>(SWS_XUB),
          *d_fact = ws.at<double>(SWS_FACT), *d_noise = bytes[SWS_NOISE] ? ws.at<double>(SWS_NOISE) : nullptr,
          *d_dist = ws.at<double>(SWS_DIST), *d_q = ws.at<double>(SWS_Q), *d_fb = ws.at<double>(SWS_FB),
-         *d_rho0 = ws.at<double>(SWS_RHO0);
+         *d_rho0 = ws.at<double>(SWS_RHO0), *d_ref = track ? ws.at<double>(TWS_REF) : nullptr,
+         *d_ee = track ? ws.at<double>(TWS_EE) : nullptr;
   int *d_best = ws.at<int>(SWS_BEST), *d_gi = ws.at<int>(SWS_GI), *d_alive = ws.at<int>(SWS_ALIVE),
-      *d_bh = ws.at<int>(SWS_BH);
+      *d_bh = ws.at<int>(SWS_BH), *d_phase = bytes[TWS_PHASE] ? ws.at<int>(TWS_PHASE) : nullptr;
   const size_t hist = history_rows(num_steps, G);
-  // src/gato_mpc_batch_sample.py:111-128: goal = endpoint 0 tiled, XU = [xstart, 0...], every
-  // row of a group at the group's start state, the hypotheses set on the solver
+  // src/gato_mpc_batch_sample.py:111-128: goal = endpoint 0 tiled (tracking: the window at offset
+  // 0), XU = [xstart, 0...], every row of a group at the group's start state, the hypotheses set
+  // on the solver
   for (size_t b = 0; b < (size_t)B; ++b)
     for (int r = 0; r < 12; ++r) xrows[b * 12 + r] = xstart[(b / H) * 12 + r];
   int rc;
   if ((rc = copy_in(h, h->d_xs, xrows.data(), xrows.size()))) return rc;
   if ((rc = copy_in(h, d_xcur, xstart, (size_t)G * 12))) return rc;
-  if ((rc = loop_start(h, start, endpoints, n_endpoints, d_ep, d_gi, d_alive))) return rc;
+  if ((rc = loop_start(h, start, gs.endpoints, gs.n_endpoints, d_ep, d_gi, d_alive))) return rc;
+  if (track && (rc = copy_in(h, d_ref, gs.ref, (size_t)gs.L * gs.ref_stride))) return rc;
+  if (d_phase) HIPCHK(hipMemcpyAsync(d_phase, gs.ref_phase, 4 * (size_t)G, hipMemcpyHostToDevice, h->stream));
   if ((rc = copy_in(h, d_fact, f_actual, 6 * (size_t)o.n_actual * G))) return rc;
   if (d_noise && (rc = copy_in(h, d_noise, noise, 3 * (size_t)num_steps * B))) return rc;
   if ((rc = copy_in(h, d_rho0, rho0.data(), rho0.size()))) return rc;
@@ -1680,7 +1730,7 @@ int i7m_mpc_run_sampled(i7m_handle* h, int32_t G, int32_t H, const double* xstar
     SampledArgs a{};
     a.N = N;
     a.H = H;
-    a.n_endpoints = n_endpoints;
+    a.n_endpoints = gs.n_endpoints;
     a.frame_world = o.frame == I7M_WRENCH_WORLD;
     a.keep_best = o.keep_best != 0;
     a.sim_dt = o.sim_dt;
@@ -1695,7 +1745,11 @@ int i7m_mpc_run_sampled(i7m_handle* h, int32_t G, int32_t H, const double* xstar
     a.best = d_best + glo;
     a.goal_idx = d_gi + glo;
     a.alive = d_alive + glo;
-    a.endpoints = d_ep;
+    a.endpoints = track ? nullptr : d_ep;
+    a.ref = d_ref;
+    a.ref_phase = d_phase ? d_phase + glo : nullptr;
+    a.L = (int)gs.L;
+    a.ref_stride = gs.ref_stride;
     int rc3;
     if ((rc3 = reset(I7M_ADMM_RESET_ALL))) return rc3;
     if ((rc3 = run_sqp(h, n, xu, out, xs, g, 3, nullptr, lo, s, mark))) return rc3;
@@ -1711,6 +1765,8 @@ int i7m_mpc_run_sampled(i7m_handle* h, int32_t G, int32_t H, const double* xstar
       a.f_actual = d_fact + ((size_t)(o.n_actual > 1 ? std::min(i, o.n_actual - 1) : 0) * G + glo) * 6;
       a.dist_out = d_dist + cur;
       a.q_out = d_q + cur * 6;
+      a.off = track && a.plant ? gs.ref_offset[i] : 0;
+      a.ee_out = track ? d_ee + cur * 3 : nullptr;
       hipLaunchKernelGGL(k_sampled_step, dim3(ng), dim3((H + 63) / 64 * 64), 0, s, h->d_model, a);
       HIPCHK(hipGetLastError());
       if (!a.plant) break;
@@ -1723,6 +1779,7 @@ int i7m_mpc_run_sampled(i7m_handle* h, int32_t G, int32_t H, const double* xstar
   if (num_steps > 0) {
     if ((rc = copy_out(h, dist_out, d_dist, hist))) return rc;
     if (q_out && (rc = copy_out(h, q_out, d_q, hist * 6))) return rc;
+    if (track && ee_out && (rc = copy_out(h, ee_out, d_ee, hist * 3))) return rc;
     if (fbest_out && (rc = copy_out(h, fbest_out, d_fb, hist * 6))) return rc;
     if (best_out) HIPCHK(hipMemcpyAsync(best_out, d_bh, 4 * hist, hipMemcpyDeviceToHost, h->stream));
   }
@@ -1730,6 +1787,36 @@ int i7m_mpc_run_sampled(i7m_handle* h, int32_t G, int32_t H, const double* xstar
   if (xu_best_out && (rc = copy_out(h, xu_best_out, d_xub, (size_t)G * T))) return rc;
   if (fhyp_out && (rc = copy_out(h, fhyp_out, h->d_fext, (size_t)B * 6))) return rc;
   return i7m_synchronize(h);
+}
+
+}  // namespace
+
+extern "C" {
+
+int i7m_mpc_run_sampled(i7m_handle* h, int32_t G, int32_t H, const double* xstart, const double* endpoints,
+                        int32_t n_endpoints, int32_t num_steps, const double* fhyp, const double* f_actual,
+                        const double* noise, const i7m_sampled_opts* opts, double* dist_out, int32_t* best_out,
+                        double* q_out, double* fbest_out, double* xcur_out, double* xu_best_out, double* fhyp_out) {
+  GoalSource gs;
+  gs.endpoints = endpoints;
+  gs.n_endpoints = n_endpoints;
+  return sampled_loop(h, "mpc_run_sampled", false, G, H, xstart, gs, num_steps, fhyp, f_actual, noise, opts, dist_out,
+                      best_out, q_out, nullptr, fbest_out, xcur_out, xu_best_out, fhyp_out);
+}
+
+int i7m_mpc_run_tracking(i7m_handle* h, int32_t G, int32_t H, const double* xstart, const double* ref, int32_t L,
+                         int32_t ref_stride, const int32_t* ref_phase, const int32_t* ref_offset, int32_t num_steps,
+                         const double* fhyp, const double* f_actual, const double* noise, const i7m_sampled_opts* opts,
+                         double* err_out, int32_t* best_out, double* q_out, double* ee_out, double* fbest_out,
+                         double* xcur_out, double* xu_best_out, double* fhyp_out) {
+  GoalSource gs;
+  gs.ref = ref;
+  gs.L = L;
+  gs.ref_stride = ref_stride;
+  gs.ref_phase = ref_phase;
+  gs.ref_offset = ref_offset;
+  return sampled_loop(h, "mpc_run_tracking", true, G, H, xstart, gs, num_steps, fhyp, f_actual, noise, opts, err_out,
+                      best_out, q_out, ee_out, fbest_out, xcur_out, xu_best_out, fhyp_out);
 }
 
 int i7m_set_timing(i7m_handle* h, int enable) {

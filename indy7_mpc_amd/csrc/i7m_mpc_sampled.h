@@ -17,6 +17,15 @@
 //   goal         d = |fk(xcur q) - goal|; below 0.095 the next endpoint (not cyclic) or, at the last
 //                one, the group stops (:203-217)
 //
+// With a reference trajectory (SampledArgs::ref, i7m_mpc_run_tracking: the deployed controller's
+// loop, gato_controller.py:201-250) the goal phase is the other goal source:
+//   goal         d = |fk(xcur q) - ref[min(ph + off, L - 1)]|, the tracking error the controller logs
+//                (:242-246), and every row of the group gets the window ref[min(ph + off + k, L - 1)],
+//                k = 0 .. N-1 (:214-216; held at the last point past the end); the group never stops
+// ph = ref_phase[g] (or 0) and off, this step's offset, is a launch argument.  All lanes write the
+// window with lane-contiguous columns, as the spread does; consecutive lanes read consecutive
+// doubles of the reference (stride 3) or three of every six (stride 6).
+//
 // The score of step i needs only (x_last, u_last), the hypotheses and the plant's result, none of
 // which the solve of step i changes, so it runs here, before that solve, and select(i) after the
 // solve only takes row `best`: the same choice the reference makes after its solve (:231).
@@ -34,6 +43,7 @@
 #pragma once
 
 #include "i7m_kernels.h"
+#include "i7m_plan.h"
 
 namespace i7m {
 
@@ -67,6 +77,12 @@ struct SampledArgs {
   double* q_out;            // (ng, 6) plant step, or null
   int* best_out;            // (ng) selected step, or null
   double* fbest_out;        // (ng, 6) selected step, or null
+  // the tracking goal source (ref != null; endpoints, goal_idx and n_endpoints are then unused)
+  const double* ref;     // (L, ref_stride) the reference, the first three of each point read
+  const int* ref_phase;  // (ng) or null (0)
+  int L, ref_stride;
+  int off;               // this step's window offset
+  double* ee_out;        // (ng, 3) plant step: the EE position of the new state, or null
 };
 
 // (error, index) minimum over the wave, the lower index on a tie: xor butterfly, every lane ends
@@ -103,6 +119,8 @@ __global__ void __launch_bounds__(256) k_sampled_step(const DevModel* __restrict
   __shared__ int s_idx[4], s_switch;
   const long r0 = (long)g * H;
   double* xub = A.xub + (long)g * T;
+  const bool track = A.ref != nullptr;  // wave-uniform: the goal source of the launch
+  const long ph = track && A.ref_phase ? A.ref_phase[g] : 0;
 
   if (A.select) {
     const int b = A.best[g];
@@ -195,16 +213,19 @@ __global__ void __launch_bounds__(256) k_sampled_step(const DevModel* __restrict
         idx = s_idx[w];
       }
     A.best[g] = idx < H ? idx : 0;
-    // the goal of the new state (src/gato_mpc_batch_sample.py:203-217)
+    // the goal of the new state (src/gato_mpc_batch_sample.py:203-217), or the window's first point
     double c[6], s[6], p[3];
     sincos6(xn, c, s);
     fk_pos(*Mg, c, s, p);
-    const double* gl = A.goals + r0 * 3 * N;
+    const double* gl = track ? A.ref + track_index(ph, A.off, 0, A.L) * A.ref_stride : A.goals + r0 * 3 * N;
     const double e0 = p[0] - gl[0], e1 = p[1] - gl[1], e2 = p[2] - gl[2];
     const double d = sqrt(e0 * e0 + e1 * e1 + e2 * e2);
     A.dist_out[g] = d;
+    if (A.ee_out)
+#pragma unroll
+      for (int k = 0; k < 3; ++k) A.ee_out[3L * g + k] = p[k];
     int sw = -1;
-    if (d < SAMPLED_GOAL_RADIUS) {
+    if (!track && d < SAMPLED_GOAL_RADIUS) {
       if (A.goal_idx[g] < A.n_endpoints - 1) {
         sw = A.goal_idx[g] + 1;
         A.goal_idx[g] = sw;
@@ -224,7 +245,14 @@ __global__ void __launch_bounds__(256) k_sampled_step(const DevModel* __restrict
   for (int e = l; e < 12 * H; e += nt) A.xs[r0 * 12 + e] = s_x[e % 12];
   __syncthreads();
   const int sw = s_switch;
-  if (sw >= 0) {
+  if (track) {
+    // the window: one load per column (knot e / 3, coordinate e % 3) and H stores
+    double* gl = A.goals + r0 * 3 * N;
+    for (int e = l; e < 3 * N; e += nt) {
+      const double v = A.ref[track_index(ph, A.off, e / 3, A.L) * A.ref_stride + e % 3];
+      for (int hh = 0; hh < H; ++hh) gl[(long)hh * 3 * N + e] = v;
+    }
+  } else if (sw >= 0) {
     double* gl = A.goals + r0 * 3 * N;
     for (int e = l; e < 3 * N * H; e += nt) gl[e] = A.endpoints[3 * sw + e % 3];
   }

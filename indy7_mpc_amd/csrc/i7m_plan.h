@@ -11,6 +11,13 @@
 
 #include "../../include/indy7_mpc.h"
 
+// functions a kernel calls too (track_index): host and device under hipcc, plain inline elsewhere
+#if defined(__HIPCC__)
+#define I7M_PLAN_HD __host__ __device__
+#else
+#define I7M_PLAN_HD
+#endif
+
 namespace i7m {
 
 // The launch knobs of a handle: i7m_config's, overridden by the environment (tuning_from_env).
@@ -258,6 +265,45 @@ inline void sampled_ws_bytes(int G, int H, int N, int num_steps, int n_endpoints
   bytes[SWS_RHO0] = 8 * B;
   bytes[SWS_BEST] = bytes[SWS_GI] = bytes[SWS_ALIVE] = 4 * (size_t)G;
   bytes[SWS_BH] = 4 * hist;
+}
+
+// ---- the reference-tracking goal source of the sampled loop (i7m_mpc_run_tracking) ---------------
+
+// Row of the reference (L points) that knot k of the window at phase ph and offset off reads: the
+// window holds the last point once it runs past the end.  The kernel's goal phase
+// (i7m_mpc_sampled.h) and the host's initial window use this one function.
+I7M_PLAN_HD inline long track_index(long ph, long off, long k, long L) {
+  const long i = ph + off + k;
+  return i < L - 1 ? i : L - 1;
+}
+// The caller's schedule: every phase (G of them, or none) and every offset >= 0.  On a refusal
+// *which names the argument and *at the entry.
+inline bool track_schedule_ok(const int32_t* ref_phase, int G, const int32_t* ref_offset, int num_steps,
+                              const char** which, int* at) {
+  for (int g = 0; ref_phase && g < G; ++g)
+    if (ref_phase[g] < 0) {
+      *which = "ref_phase";
+      *at = g;
+      return false;
+    }
+  for (int i = 0; i < num_steps; ++i)
+    if (ref_offset[i] < 0) {
+      *which = "ref_offset";
+      *at = i;
+      return false;
+    }
+  return true;
+}
+// The sampled loop's request with either goal source: sampled_ws_bytes' 13 sub-buffers, then the
+// reference (L, ref_stride), the groups' phases and the EE history.  Endpoint mode (L = 0): those
+// three are empty and take no room, so its allocation is what it was.
+enum { TWS_REF = SAMPLED_WS_COUNT, TWS_PHASE, TWS_EE, TRACKING_WS_COUNT };
+inline void tracking_ws_bytes(int G, int H, int N, int num_steps, int n_endpoints, int n_actual, bool noise, long L,
+                              int ref_stride, bool phase, size_t bytes[TRACKING_WS_COUNT]) {
+  sampled_ws_bytes(G, H, N, num_steps, n_endpoints, n_actual, noise, bytes);
+  bytes[TWS_REF] = 8 * (size_t)L * ref_stride;
+  bytes[TWS_PHASE] = L > 0 && phase ? 4 * (size_t)G : 0;
+  bytes[TWS_EE] = L > 0 ? 3 * 8 * history_rows(num_steps, G) : 0;
 }
 
 }  // namespace i7m

@@ -16,10 +16,23 @@ What differs from the reference, on purpose:
     :170-187, never triggers then);
   * ``resample_f_ext=True`` perturbs every row but row 0 (:291-298: keep_best = 0, decay = 1);
     pass ``keep_best=True, decay=0.97`` for the controller's rule (gato_controller.py:120-129).
+
+``run_tracking`` / ``run_tracking_groups`` are the deployed controller's loop
+(``GATO_Controller.joint_callback``, gato_controller.py:201-250: the N-knot goal window slides along
+a reference trajectory, ``i7m_mpc_run_tracking``).  What differs from ``GATO_Controller``:
+  * the plant is the device's rk4 step of ``sim_dt``, not MuJoCo at wall-clock intervals, so the
+    window's offset follows the schedule floor((i + 1) sim_dt / dt) (or the caller's);
+  * the first step scores the hypotheses with the initial solve's control, where the controller
+    starts from u_last = 0 (:206);
+  * ties go to the lowest index, the device's rule, where the controller's ``<=`` (:115) takes the
+    highest; tied hypotheses are identical rows, so the trajectories are the same;
+  * the actual force is the caller's schedule (``f_actual``), not the controller's clipped random
+    walk (:236-239).
 """
 from __future__ import annotations
 
 import time
+from fractions import Fraction
 
 import numpy as np
 
@@ -27,6 +40,17 @@ from . import _lib
 from .model import default_model
 
 _SIZES = (1, 2, 4, 8, 16, 32, 64, 128, 256)
+
+
+def tracking_schedule(sim_dt, sim_time, dt):
+    """(num_steps, offsets) of a tracking run: floor(sim_time / sim_dt) control steps, and at step i
+    the window has slid by floor((i + 1) sim_dt / dt) points (gato_controller.py:214-215 with a
+    constant elapsed time of sim_dt).  In exact rational arithmetic on the decimal values the
+    floats print as, so that 0.001 / 0.01 is 1 / 10 and the window moves at steps 9, 19, ...:
+    accumulated floats would move it a step late or early."""
+    sim_dt, sim_time, dt = (Fraction(repr(float(v))) for v in (sim_dt, sim_time, dt))
+    num_steps = int(sim_time / sim_dt)
+    return num_steps, np.array([int((i + 1) * sim_dt / dt) for i in range(num_steps)], dtype=np.int32)
 
 
 class MPC_GATO_Batch_Sample:
@@ -101,6 +125,59 @@ class MPC_GATO_Batch_Sample:
         }
         self.last = r
         return xpaths, stats
+
+    def run_tracking_groups(self, xstarts, ref_traj, sim_dt=0.01, sim_time=5, f_actual=None, ref_phase=None,
+                            ref_offset=None):
+        """G independent controllers tracking ref_traj (i7m_mpc_run_tracking), one per row of xstarts
+        (G, 12), group g starting at point ref_phase[g] of the reference (default 0).  ref_traj: flat
+        with six entries per point (as utils.figure8 builds it), or (L, 3) / (L, 6).  ref_offset
+        (num_steps,): the window's offset at every step; default floor((i + 1) sim_dt / dt).
+        f_actual as run_mpc_groups'.  Returns the controller's stats (tracking_errors
+        (num_steps, G), ee_positions and ee_ref_positions (num_steps, G, 3), joint_positions
+        (num_steps, G, 6), solve_times) plus 'best_ids' and 'f_ext_best'."""
+        xs = np.asarray(xstarts, float).reshape(-1, 12)
+        G, H = xs.shape[0], self.batch_size
+        ref = np.asarray(ref_traj, float)
+        if ref.ndim == 1:
+            ref = ref.reshape(-1, 6)
+        if ref.ndim != 2 or ref.shape[1] not in (3, 6) or ref.shape[0] < 1:
+            raise ValueError("ref_traj must be flat with 6 entries per point, (L, 3) or (L, 6)")
+        if ref_offset is None:
+            num_steps, ref_offset = tracking_schedule(sim_dt, sim_time, self.dt)
+        ref_offset = np.asarray(ref_offset, dtype=np.int32).reshape(-1)
+        num_steps = len(ref_offset)
+        phase = np.zeros(G, np.int32) if ref_phase is None else np.asarray(ref_phase, dtype=np.int32).reshape(G)
+        fa = np.tile(self.actual_f_ext, (G, 1)) if f_actual is None else np.asarray(f_actual, float)
+        if fa.size == 6:
+            fa = np.tile(fa.reshape(6), (G, 1))
+        noise = None
+        if self.resample_f_ext:
+            noise = self.rng.normal(0, self.f_ext_resample_std, (num_steps, G * H, 6))[:, :, :3]
+        h = self._handle(G * H)
+        t0 = time.perf_counter()
+        r = h.mpc_run_tracking(xs, ref, ref_offset, np.tile(self.f_ext_batch, (G, 1)), fa, ref_phase=phase, noise=noise,
+                               sim_dt=sim_dt, frame="world", reset_what=_lib.ADMM_RESET_ALL, keep_best=self.keep_best,
+                               decay=self.decay)
+        per_step = (time.perf_counter() - t0) / max(num_steps, 1)
+        self.f_ext_batch = r["fhyp"][:H].copy()
+        first = np.minimum(phase[None, :].astype(np.int64) + ref_offset[:, None], ref.shape[0] - 1)
+        self.last = r
+        return {
+            "tracking_errors": r["err"],
+            "ee_positions": r["ee"],
+            "ee_ref_positions": ref[first, :3],
+            "joint_positions": r["q"],
+            "solve_times": [round(per_step, 5)] * num_steps,  # the device loop's mean time per step
+            "best_ids": r["best"],
+            "f_ext_best": r["fbest"],
+        }
+
+    def run_tracking(self, xstart, ref_traj, sim_dt=0.01, sim_time=5, f_actual=None):
+        """One controller tracking ref_traj, as the deployed GATO_Controller does between two joint
+        states (gato_controller.py:201-250): the stats of run_tracking_groups with one entry per
+        control step (no group axis)."""
+        st = self.run_tracking_groups(np.asarray(xstart, float).reshape(1, 12), ref_traj, sim_dt, sim_time, f_actual)
+        return {k: (v if k == "solve_times" else v[:, 0]) for k, v in st.items()}
 
     def run_mpc(self, xstart, endpoints, sim_dt=0.001, sim_time=5):
         """One controller, as the reference's run_mpc (src/gato_mpc_batch_sample.py:106-252):

@@ -71,6 +71,30 @@ def rk4(model, data, q, v, u, dt, f_ext=None):
     return qo[0], vo[0]
 
 
+def figure8(A_x, A_z, offset, period, dt, cycles, angle=np.pi / 4):
+    """The controller's figure-8 reference (gato_controller.py's figure8, called at :316-320), flat
+    with six entries [x y z 0 0 0] per point and ``int(period / dt)`` points per cycle, ``cycles``
+    times over.  With t = linspace(0, 2 pi, int(period / dt)) the unrotated point is
+    (o_x + A_x sin t, o_y, o_z + A_z sin(2 t) / 2 + A_z / 2); it is rotated about z by ``angle``.
+    ``offset`` is (o_x, o_y, o_z) or one number for all three."""
+    o = np.broadcast_to(np.asarray(offset, dtype=float), (3,))
+    t = np.linspace(0.0, 2.0 * np.pi, int(period / dt))
+    x = o[0] + A_x * np.sin(t)
+    y = np.full_like(t, o[1])
+    z = o[2] + A_z * np.sin(2.0 * t) / 2.0 + A_z / 2.0
+    c, s = np.cos(angle), np.sin(angle)
+    pts = np.zeros((t.size, 6))
+    pts[:, 0] = c * x - s * y
+    pts[:, 1] = s * x + c * y
+    pts[:, 2] = z
+    return np.tile(pts.reshape(-1), int(cycles))
+
+
+def figure_8(x_amplitude, z_amplitude, offset, timestep, period, num_periods, angle_offset=np.pi / 4):
+    """The ROS package's spelling of figure8 (src/mpc/mpc/reference_traj.py:4)."""
+    return figure8(x_amplitude, z_amplitude, offset, period, timestep, num_periods, angle=angle_offset)
+
+
 def print_stats(stats):
     """reference src/utils.py:23-39."""
     for task, stat in stats.items():
