@@ -64,15 +64,9 @@ struct AdmmArgs {
 // factor packed lower-triangular (171 of 324), the scaled J_k as its q rows' two diagonals
 // (E_i D_i for I, E_i dt D_{6+i} for dt I) and its v rows (6 x 18): 120 of 216.  Staged to LDS
 // unpacked, so the arithmetic is the dense form's (the dropped entries are exact zeros).
-#ifndef I7M_ADMM_FSTRIDE
-#define I7M_ADMM_FSTRIDE 19  // the register factor's LDS row stride for S and C (18: 3-way bank conflicts on row reads)
-#endif
-#ifndef I7M_ADMM_SCALE_WPE
-#define I7M_ADMM_SCALE_WPE 2  // (N <= 32: the linearisation magnitudes stay in registers for all ten passes)
-#endif
-#ifndef I7M_ADMM_FACTOR_WPE
-#define I7M_ADMM_FACTOR_WPE 2
-#endif
+constexpr int ADMM_FSTRIDE = 19;  // the register factor's LDS row stride for S and C (18: 3-way bank conflicts on row reads)
+constexpr int ADMM_SCALE_WPE = 2;  // (N <= 32: the linearisation magnitudes stay in registers for all ten passes)
+constexpr int ADMM_FACTOR_WPE = 2;
 // One record per stage, N per problem (problem b's at R + b N ADM_REC): [Linv_k | compact J_k]
 // = 300 doubles (150 pieces of 16 B).  Linv_k's rows 0-15 are stored lower-triangular, each padded
 // to an even width (a zero after the diagonal of the even rows: 144 doubles), rows 16 and 17 in full
@@ -549,7 +543,7 @@ constexpr int AF_STG = 256;
 __device__ __forceinline__ void adm_factor(const AdmmArgs& a, int N, double rho, const double* Pq, const double* Pd, const double* Ib,
                            double* Rb, double* sS, double* sJ, double* sL, double* sCp, double* stg, int l0) {
   const double re = 1e3 * rho, sigma = a.A.sigma;
-  constexpr int FS = I7M_ADMM_FSTRIDE;  // row stride of S and C_{k-1} in LDS
+  constexpr int FS = ADMM_FSTRIDE;  // row stride of S and C_{k-1} in LDS
   double* sCol = sL + 324;  // (the sweeps' C slot, free while factoring)
   const auto rA = a4_rsrc(a.abase, a.abytes);
   auto boff = [&](const double* q) { return (unsigned)__builtin_amdgcn_readfirstlane((int)((const char*)q - (const char*)a.abase)); };
@@ -713,7 +707,7 @@ __device__ __forceinline__ void admm_body(const AdmmArgs& a) {
   if (b >= P.B || (a.active && !a.active[b])) return;
   const int l = threadIdx.x, N = P.N, T = P.T, m = 12 * N;
   constexpr bool FAC = (PH & 8) != 0;
-  __shared__ double sB[(PH & 1) ? 64 * CT : 756], sS[FAC ? 18 * I7M_ADMM_FSTRIDE : 1], sCp[FAC ? 12 * I7M_ADMM_FSTRIDE : 1];
+  __shared__ double sB[(PH & 1) ? 64 * CT : 756], sS[FAC ? 18 * ADMM_FSTRIDE : 1], sCp[FAC ? 12 * ADMM_FSTRIDE : 1];
   __shared__ double sD[(PH & 1) ? 64 * CT : 1], sE[(PH & 1) ? 64 * (2 * CT / 3) : 1], sRM[(PH & 1) ? 64 * (2 * CT / 3) : 1],
       sCO[(PH & 1) ? (64 * CT / 18 + 1) * COST_STRIDE : 1], sStg[FAC ? 2 * AF_STG : 1];
   double* sL = sB;
@@ -744,11 +738,11 @@ __device__ __forceinline__ void admm_body(const AdmmArgs& a) {
 }
 
 template <int CT>  // columns of [P; A] per lane: 9 for N <= 32, 18 for N <= 64
-__global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(I7M_ADMM_SCALE_WPE, I7M_ADMM_SCALE_WPE)))
+__global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(ADMM_SCALE_WPE, ADMM_SCALE_WPE)))
 k_admm_scale(AdmmArgs a) {
   admm_body<1, CT>(a);
 }
-__global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(I7M_ADMM_FACTOR_WPE, I7M_ADMM_FACTOR_WPE)))
+__global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(ADMM_FACTOR_WPE, ADMM_FACTOR_WPE)))
 k_admm_factor(AdmmArgs a) {
   admm_body<8, 1>(a);
 }

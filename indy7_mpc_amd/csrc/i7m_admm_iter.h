@@ -746,7 +746,7 @@ __device__ __forceinline__ void admm_iter4(const AdmmArgs& a) {
             const double rq = __shfl(rho, 16 * q, 64);
             double* scr = ring;
             adm_factor(a, N, rq, a.Pq + bq2 * N * 36, a.Pd + bq2 * T, a.I + bq2 * m, a.R + bq2 * N * ADM_REC, scr,
-                       scr + 30 * I7M_ADMM_FSTRIDE + 388, scr + 30 * I7M_ADMM_FSTRIDE, scr + 18 * I7M_ADMM_FSTRIDE,
+                       scr + 30 * ADMM_FSTRIDE + 388, scr + 30 * ADMM_FSTRIDE, scr + 18 * ADMM_FSTRIDE,
                        scr + 2048, l);
           }
           __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");

@@ -358,40 +358,12 @@ int launch_linearize(i7m_handle* h, hipStream_t s, const Bufs& W, const SolvePar
   });
 }
 
-template <int ABL>
-void launch_riccati_mfma(hipStream_t s, hipEvent_t ea, hipEvent_t eb, const Bufs& W, const SolveParams& P,
-                         const double* xu, const double* xs, const int* active, double* sol) {
-  hipExtLaunchKernelGGL(k_riccati_mfma<ABL>, dim3(P.B), dim3(64), 0, s, ea, eb, 0, P, xu, xs, W.lin, W.cost, W.qpd, active,
-                        W.kbuf, sol, (const double*)nullptr, (const double*)nullptr, (double*)nullptr);
-}
-
 // vout (i7m_qp_value): the first knot's cost-to-go V~_0 (B, 13, 13) instead of the rollout (one-wave
 // kernel only)
 int launch_riccati(i7m_handle* h, hipStream_t s, const Bufs& W, const SolveParams& P, const double* xu,
                    const double* xs, const int* active, double* sol, double* vout = nullptr) {
   if (P.B == 0) return I7M_OK;
   return timed(h, s, I7M_K_RICCATI, [&](hipEvent_t ea, hipEvent_t eb) {
-#ifdef I7M_DIAG
-    if (!vout) {
-    // I7M_ABLATE -> ABL bits of riccati_mfma_body (diagnostic timing builds, results invalid;
-    // compiled only into the -DI7M_DIAG library that tools/ load, never the shipping one)
-    bool ablated = true;
-    switch (h->ablate) {
-      case 1: launch_riccati_mfma<1>(s, ea, eb, W, P, xu, xs, active, sol); break;      // no rollout
-      case 2: launch_riccati_mfma<6>(s, ea, eb, W, P, xu, xs, active, sol); break;      // scaling for GJ
-      case 8: launch_riccati_mfma<4>(s, ea, eb, W, P, xu, xs, active, sol); break;      // LDS-exchange GJ
-      case 10: launch_riccati_mfma<8>(s, ea, eb, W, P, xu, xs, active, sol); break;     // kbuf slot 0
-      case 11: launch_riccati_mfma<24>(s, ea, eb, W, P, xu, xs, active, sol); break;    // + lin slot 0
-      case 13: launch_riccati_mfma<32>(s, ea, eb, W, P, xu, xs, active, sol); break;    // rollout dead
-      case 18: launch_riccati_mfma<448>(s, ea, eb, W, P, xu, xs, active, sol); break;   // rollout chain only
-      case 19: launch_riccati_mfma<513>(s, ea, eb, W, P, xu, xs, active, sol); break;   // phase timestamps, no rollout
-      default: ablated = false;
-    }
-    if (ablated) return;
-    }
-#endif
-    // (the diag library's default path is the release selection below, so its per-wave timelines
-    // show the shipping kernels)
     const RicVariant rv = riccati_variant(h->tune, P.B, vout != nullptr);
     if (rv.w2) {
       auto go2 = [&](auto kern) {
@@ -407,20 +379,20 @@ int launch_riccati(i7m_handle* h, hipStream_t s, const Bufs& W, const SolveParam
                             sol, (const double*)nullptr, (const double*)nullptr, vout);
     };
     switch (rv.bc) {
-      case 1: go(k_riccati_mfma<0, false, 1>); break;
-      case 2: go(k_riccati_mfma<0, false, 2>); break;
-      case 3: go(k_riccati_mfma<0, false, 3>); break;
-      case 6: go(k_riccati_mfma<0, false, 6>); break;
-      case 7: go(k_riccati_mfma<0, false, 7>); break;
-      default: go(k_riccati_mfma<0, false, 0>);
+      case 1: go(k_riccati_mfma<false, 1>); break;
+      case 2: go(k_riccati_mfma<false, 2>); break;
+      case 3: go(k_riccati_mfma<false, 3>); break;
+      case 6: go(k_riccati_mfma<false, 6>); break;
+      case 7: go(k_riccati_mfma<false, 7>); break;
+      default: go(k_riccati_mfma<false, 0>);
     }
   });
 }
 
-// k_linesearch<spec, 0, waves, world_wrench> (waves 1, 2 or 4; 64 threads per wave)
+// k_linesearch<spec, waves, world_wrench> (waves 1, 2 or 4; 64 threads per wave)
 template <bool SPEC, bool FW>
 auto ls_kernel_w(int waves) {
-  return waves == 4 ? k_linesearch<SPEC, 0, 4, FW> : waves == 2 ? k_linesearch<SPEC, 0, 2, FW> : k_linesearch<SPEC, 0, 1, FW>;
+  return waves == 4 ? k_linesearch<SPEC, 4, FW> : waves == 2 ? k_linesearch<SPEC, 2, FW> : k_linesearch<SPEC, 1, FW>;
 }
 auto ls_kernel(bool spec, bool world_wrench, int waves) {
   if (spec) return world_wrench ? ls_kernel_w<true, true>(waves) : ls_kernel_w<true, false>(waves);
@@ -458,17 +430,9 @@ int launch_linesearch(i7m_handle* h, hipStream_t s, const Bufs& W, const SolvePa
     });
   }
   return timed(h, s, I7M_K_LINESEARCH, [&](hipEvent_t ea, hipEvent_t eb) {
-    auto go = [&](auto kern, int threads) {
-      hipExtLaunchKernelGGL(kern, dim3(P.B), dim3(threads), lds, s, ea, eb, 0, h->d_model, P, xu, xu_out, sol, goals, W.fext,
-                            active, st, alpha_out, iter, mode, ln, cs, LsSplit{});
-    };
-#ifdef I7M_DIAG
-    if (h->ablate == 4 && nw == 1) {
-      go(k_linesearch<true, 1>, 64);
-      return;
-    }
-#endif
-    go(ls_kernel(h->spec, fw, nw), 64 * nw);  // (two waves: A/B only, I7M_LS_WAVES=2)
+    // (two waves: A/B only, I7M_LS_WAVES=2)
+    hipExtLaunchKernelGGL(ls_kernel(h->spec, fw, nw), dim3(P.B), dim3(64 * nw), lds, s, ea, eb, 0, h->d_model, P, xu, xu_out,
+                          sol, goals, W.fext, active, st, alpha_out, iter, mode, ln, cs, LsSplit{});
   });
 }
 
@@ -585,7 +549,7 @@ int solve_qp(i7m_handle* h, hipStream_t s, const Bufs& W, const SolveParams& P, 
   for (int it = 0; it < BP.max_iters; ++it) {
     for (int half = 0; half < 2; ++half) {
       rc = timed(h, s, I7M_K_RICCATI_BOX, [&](hipEvent_t ea, hipEvent_t eb) {
-        hipExtLaunchKernelGGL((k_riccati_mfma<0, true>), g, blk, 0, s, ea, eb, 0, P, xu, xs, W.lin, W.cost, W.qpd, W.bact, W.kbuf,
+        hipExtLaunchKernelGGL((k_riccati_mfma<true>), g, blk, 0, s, ea, eb, 0, P, xu, xs, W.lin, W.cost, W.qpd, W.bact, W.kbuf,
                            sol, W.bsig, W.bh, (double*)nullptr);
       });
       if (rc) return rc;
@@ -658,7 +622,7 @@ int run_sqp(i7m_handle* h, int B, const double* d_xu_in, double* d_xu, const dou
     if ((rc = solve_qp(h, s, W, P, xin, d_xs, act, qbuf, &qsol, it, mark))) return rc;
     // mode 2: the ADMM mode's QP solver carries state, so an alpha = 0 iteration is re-solved
     if ((rc = launch_linesearch(h, s, W, P, xin, d_xu, qsol, d_goals, act, d_st, nullptr, it,
-                                h->cfg.qp_mode == I7M_QP_ADMM ? 2 : 0, h->ablate != 6)))
+                                h->cfg.qp_mode == I7M_QP_ADMM ? 2 : 0, true)))
       return rc;
   }
   return I7M_OK;
@@ -1177,7 +1141,11 @@ int i7m_create(const i7m_config* cfg, i7m_handle** out) {
     return bail(fail(I7M_EHIP, "hipStreamCreate failed"));
   h->stream = h->own;
 #ifdef I7M_DIAG
-  if (const char* e = std::getenv("I7M_ABLATE")) h->ablate = std::atoi(e);
+  if (const char* e = std::getenv("I7M_ABLATE")) {
+    h->ablate = std::atoi(e);
+    const AblateStatus as = ablate_status(h->ablate);
+    if (as.kind != Ablate::known) return bail(fail(I7M_EINVAL, std::string("I7M_ABLATE=") + e + ": " + as.msg));
+  }
 #else
   if (std::getenv("I7M_ABLATE"))
     return bail(fail(I7M_EINVAL, "I7M_ABLATE is set, but this is the release library: the ablation "

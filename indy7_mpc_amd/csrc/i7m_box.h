@@ -1,6 +1,6 @@
 // i7m_box.h — interior-point iteration of the box-constrained QP mode (I7M_QP_BOX, SURVEY.md
 // §8d config 4).  Restates oracle/box_ipm.py::ipm_box step by step; the Newton steps
-// themselves are k_riccati_mfma<0, true> (i7m_riccati_mfma.h) on the same linearisation.
+// themselves are k_riccati_mfma<true> (i7m_riccati_mfma.h) on the same linearisation.
 //
 // One wavefront per problem, lanes strided over the T = 18N-6 trajectory entries.  Per
 // problem, in (B, T) device arrays: the iterate x, the bound duals z_l / z_u, the Riccati
@@ -11,17 +11,13 @@
 #include "i7m_kernels.h"
 #include "i7m_riccati_mfma.h"
 
-#ifndef I7M_IPM_WPE
-#define I7M_IPM_WPE 4
-#endif
+namespace i7m {
+
+constexpr int IPM_WPE = 4;  // waves per SIMD k_ipm_fused is compiled for
 // cross-lane broadcasts of the box body's Newton steps (riccati_mfma_body BC): 3 = the rollout's and
 // the pivots' by DPP (5.45 -> 5.42 ms per k_ipm_fused launch against 2, the rollout's only; bit-identical;
 // DESIGN.md §4.2)
-#ifndef I7M_IPM_BC
-#define I7M_IPM_BC 3
-#endif
-
-namespace i7m {
+constexpr int IPM_BC = 3;
 
 struct BoxParams {
   int mask;       // I7M_BOX_Q | I7M_BOX_V | I7M_BOX_U
@@ -170,10 +166,7 @@ __device__ __forceinline__ IpmState ipm_init_body(const BoxTab& Bt, const SolveP
 // flight instead of waiting out the memory latency element by element.  The per-lane order of
 // every accumulation is unchanged (chunks and their elements in increasing e), so the results
 // are bit-identical to the element-by-element loops.
-#ifndef I7M_IPM_U
-#define I7M_IPM_U 6
-#endif
-constexpr int IPM_U = I7M_IPM_U;
+constexpr int IPM_U = 6;
 
 __device__ __forceinline__ void ipm_pred_body(const BoxTab& Bt, const SolveParams& P, const BoxParams& BP, const int b,
                                               const double* __restrict__ y, const double* __restrict__ x,
@@ -425,7 +418,7 @@ __global__ void __launch_bounds__(64) k_ipm_corr(const DevModel* __restrict__ Mg
 // iteration count and the iteration state stays in registers.
 // !DELTA (default): both Newton steps are full Riccati solves, the same arithmetic as the split
 // kernels phase for phase.  DELTA (I7M_IPM=delta): the predictor step is a full
-// riccati_mfma_body<0, true, true> (which also stores every stage's H^-1) and the corrector
+// riccati_mfma_body<true, true> (which also stores every stage's H^-1) and the corrector
 // reuses that factorisation (riccati_delta_body: same Hessian, only the linear terms change by
 // dh).  Measured slower (14.7 vs 13.7 ms per QP at B = 4096, N = 64): the vector pass streams
 // as many bytes per stage as the full step and is as latency-bound.
@@ -464,7 +457,7 @@ __device__ __forceinline__ const IpmFusedArgs* kernarg_ipm() {
 }
 
 template <bool DELTA>
-__global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(I7M_IPM_WPE, I7M_IPM_WPE)))
+__global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(IPM_WPE, IPM_WPE)))
 k_ipm_fused(IpmFusedArgs args) {
   I7M_TL(4);
   const int b = blockIdx.x;
@@ -501,11 +494,11 @@ k_ipm_fused(IpmFusedArgs args) {
     if (skip_newton) {
     } else if (!DELTA) {
       // the corrector (half 1) stores only K~'s feedforward column: its gain is the predictor's
-      riccati_mfma_body<0, true, false, I7M_IPM_BC>(b, P, A->xu, A->xs, A->lin, A->cost, A->qpd, A->kbuf, A->y, A->sig,
-                                                    A->h, sh, l, nullptr, half == 1);
+      riccati_mfma_body<true, false, IPM_BC>(b, P, A->xu, A->xs, A->lin, A->cost, A->qpd, A->kbuf, A->y, A->sig, A->h,
+                                             sh, l, nullptr, half == 1);
     } else if (half == 0) {
-      riccati_mfma_body<0, true, true>(b, P, A->xu, A->xs, A->lin, A->cost, A->qpd, A->kbuf, A->y, A->sig, A->h, sh, l,
-                                       A->hinv);
+      riccati_mfma_body<true, true>(b, P, A->xu, A->xs, A->lin, A->cost, A->qpd, A->kbuf, A->y, A->sig, A->h, sh, l,
+                                    A->hinv);
     } else {
       riccati_delta_body(b, P, A->lin, A->kbuf, A->hinv, A->dh, A->y, sh, l);
     }
@@ -513,7 +506,7 @@ k_ipm_fused(IpmFusedArgs args) {
     const IpmFusedArgs* B = kernarg_ipm();
     const BoxParams BP = B->BP;
     // the most work left first: remaining iterations ~ log(mu / tol) (mu_0 = z0 = 0.1, tol 1e-8)
-    if (I7M_PRIO & 4) set_prio((int)(log10(fmax(S.mu / BP.tol, 1.0)) * (1.0 / 2.5)));
+    set_prio((int)(log10(fmax(S.mu / BP.tol, 1.0)) * (1.0 / 2.5)));
     if (half == 0) {
       if (!skip_pred) {
         ipm_pred_body(Bt, B->P, BP, b, B->y, B->x, B->zl, B->zu, B->dxa, B->h, S, DELTA ? B->dh : nullptr);

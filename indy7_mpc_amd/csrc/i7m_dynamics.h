@@ -36,32 +36,19 @@ __device__ __forceinline__ void lds_sync() {
 // lds_sync() compiles to; in a multi-wave workgroup (k_sqp_fused) the other waves need not
 // take part.
 //   A wavefront's LDS instructions execute in order, so within one wave only the compiler's order
-// matters: I7M_WAVE_SYNC_FENCE 0 (default) keeps it with an empty asm with a memory clobber; 1 emits
+// matters: wave_sync() keeps it with an empty asm with a memory clobber; wave_sync_fence() emits
 // the fences, whose s_waitcnt lgkmcnt(0) also drains every outstanding LDS operation.  (No kernel
 // here writes LDS by direct-from-memory loads, whose completion is not ordered with ds_* ops.)
-#ifndef I7M_WAVE_SYNC_FENCE
-#define I7M_WAVE_SYNC_FENCE 0
-#endif
 __device__ __forceinline__ void wave_sync_fence() {
   __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup", "local");
   __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup", "local");
 }
-__device__ __forceinline__ void wave_sync() {
-#if I7M_WAVE_SYNC_FENCE
-  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup", "local");
-  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup", "local");
-#else
-  __asm__ volatile("" ::: "memory");
-#endif
-}
+__device__ __forceinline__ void wave_sync() { __asm__ volatile("" ::: "memory"); }
 // Wave priority (s_setprio 0..3; the SIMD's instruction arbiter otherwise favours the oldest
 // wave).  The Riccati recursion sets it by progress (riccati_mfma_body, BC bit 2: equal-work
-// waves, the one furthest behind first).  I7M_PRIO bits: 1 the line-search rounds, later rounds
-// first (measured no change: 78.4 vs 78.8 us at B = 4096, not default), 2 the interior-point
-// iterations of k_ipm_fused, the most work left first (6.00 -> 5.92 ms per QP, default).
-#ifndef I7M_PRIO
-#define I7M_PRIO 4
-#endif
+// waves, the one furthest behind first), and k_ipm_fused by the interior-point iterations left,
+// the most work first (6.00 -> 5.92 ms per QP).  The line-search rounds, later rounds first,
+// measured no change (78.4 vs 78.8 us at B = 4096) and set none.
 __device__ __forceinline__ void set_prio(int p) {  // p wave-uniform; s_setprio takes an immediate
   if (p <= 0) __builtin_amdgcn_s_setprio(0);
   else if (p == 1) __builtin_amdgcn_s_setprio(1);

@@ -81,11 +81,11 @@ k_sqp_fused(const DevModel* __restrict__ Mg, SolveParams P, const double* xu_in,
     }
     block_sync_global();
     // 2. the QP (wave 0; its lane id is not re-read: that crashes this compiler)
-    if (w == 0) riccati_mfma_body<0, false>(b, P, xin, xs, lin, cost, qpd, kbuf, sol, nullptr, nullptr, fsm, l);
+    if (w == 0) riccati_mfma_body<false>(b, P, xin, xs, lin, cost, qpd, kbuf, sol, nullptr, nullptr, fsm, l);
     block_sync_global();
     // 3. line search and step; clears active[b] when the SQP loop ends (src/osqp_sqp.py:81-91)
-    linesearch_body<SPEC, 0, W, FW>(Mg, P, b, w, phase_lane(lane_ids), fsm, merit, xin, xu_out, sol, goals, fext,
-                                    active, stats, nullptr, it, 0, lin, cost);
+    linesearch_body<SPEC, W, FW>(Mg, P, b, w, phase_lane(lane_ids), fsm, merit, xin, xu_out, sol, goals, fext,
+                                 active, stats, nullptr, it, 0, lin, cost);
     if (LOOP) {
       block_sync_global();
       if (!*(volatile int*)(active + b)) break;

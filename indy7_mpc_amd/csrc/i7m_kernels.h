@@ -141,28 +141,22 @@ struct alignas(16) XD {
 // ahead of its arithmetic.  (As a separate inlined function the kernel allocates spill-free;
 // written in the round loop it spilled, 115 -> 110 us.)
 // FW: f6 is a world-frame wrench, converted to joint 6's frame at this knot's configuration.
-// I7M_LS_NOSEL (default 1): the base point (candidate 0, al = 0) is XU + 0 (sol - XU), equal to XU
-// for every finite step entry but for the sign of an exact zero, so the point values need no
-// per-value select between x and x + al d (two v_cndmask per value, ~100 per evaluation); the
-// base merit of the SQP loop comes from the linearisation anyway, candidate 0 is evaluated only
-// without it.
-#ifndef I7M_LS_NOSEL
-#define I7M_LS_NOSEL 1
-#endif
-__device__ __forceinline__ double ls_pick(bool base_pt, double x, double v) { return (I7M_LS_NOSEL || !base_pt) ? v : x; }
+// The base point (candidate 0, al = 0) is XU + 0 (sol - XU), equal to XU for every finite step
+// entry but for the sign of an exact zero, so the point values need no per-value select between
+// x and x + al d (two v_cndmask per value, ~100 per evaluation); the base merit of the SQP loop
+// comes from the linearisation anyway, candidate 0 is evaluated only without it.
 template <bool SPEC, bool FW = false>
 __device__ __forceinline__ void ls_merit_terms(const DevModel* __restrict__ Mg, const SolveParams& P, const int k,
-                                                      const bool last, const bool base_pt, const double al,
+                                                      const bool last, const double al,
                                                       const XD* sXD, const double* goal,
                                                       const double* f6, double* fpark, double* o) {
   const DevModel& Md = SPEC ? kIndy7Model : *Mg;
   const int ok = 18 * k, on = 18 * (last ? k : k + 1);
-  // both halves of the pair in one 16-byte read and a select (written as `base_pt ? x : x + al d`
-  // the compiler made the d read a branch of its own, serialising every knot value's LDS reads)
+  // both halves of the pair in one 16-byte read (with a per-value `base_pt ? x : x + al d` the
+  // compiler made the d read a branch of its own, serialising every knot value's LDS reads)
   auto val = [&](int e) -> double {
     const XD p = sXD[e];
-    const double v = p.x + al * p.d;
-    return ls_pick(base_pt, p.x, v);
+    return p.x + al * p.d;
   };
   double c[6], sn[6], pe[3];
   {
@@ -187,9 +181,8 @@ __device__ __forceinline__ void ls_merit_terms(const DevModel* __restrict__ Mg, 
     __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
     for (int i = 0; i < 6; ++i) {
-      const double vi = pv[i].x + al * pv[i].d, ui = pu[i].x + al * pu[i].d;
-      v[i] = ls_pick(base_pt, pv[i].x, vi);
-      u[i] = ls_pick(base_pt, pu[i].x, ui);
+      v[i] = pv[i].x + al * pv[i].d;
+      u[i] = pu[i].x + al * pu[i].d;
       vv += v[i] * v[i];
     }
   }
@@ -224,10 +217,7 @@ __device__ __forceinline__ void ls_merit_terms(const DevModel* __restrict__ Mg, 
       __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
       for (int i = 0; i < 3; ++i) {
-        auto pt = [&](const XD& p) {
-          const double v = p.x + al * p.d;
-          return ls_pick(base_pt, p.x, v);
-        };
+        auto pt = [&](const XD& p) { return p.x + al * p.d; };
         const double xq = pt(pq[i]), xv = pt(pv[i]), nq = pt(pn[i]), nv = pt(pw[i]);
         const double dq = (xq + xv * P.dt) - nq;
         const double dv = (xv + a[3 * hf + i] * P.dt) - nv;
@@ -291,16 +281,13 @@ __device__ __forceinline__ const LsKernArgs* kernarg_ls() {
 // k_linesearch, and the third phase of each SQP iteration of k_sqp_fused.  ls_dyn: the dynamic
 // LDS of ls_lds_bytes(T, W); merit: 9 doubles of LDS.
 // LDS ordering inside the line search: with one wave per problem (W = 1) its LDS instructions
-// execute in order, so a compiler barrier is enough (I7M_LS_WSYNC 1); with W waves, lds_sync.
-#ifndef I7M_LS_WSYNC
-#define I7M_LS_WSYNC 1
-#endif
+// execute in order, so a compiler barrier is enough; with W waves, lds_sync.
 template <int W>
 __device__ __forceinline__ void ls_sync() {
-  if constexpr (W == 1 && I7M_LS_WSYNC) __asm__ volatile("" ::: "memory");
+  if constexpr (W == 1) __asm__ volatile("" ::: "memory");
   else lds_sync();
 }
-template <bool SPEC, int ABL = 0, int W = 1, bool FW = false, bool KA = false>
+template <bool SPEC, int W = 1, bool FW = false, bool KA = false>
 __device__ __forceinline__ void linesearch_body(const DevModel* __restrict__ Mg, const SolveParams& P, const int b,
                                                 const int w, const int l, double* __restrict__ ls_dyn,
                                                 double* __restrict__ merit, const double* xu, double* xu_out,
@@ -356,7 +343,7 @@ __device__ __forceinline__ void linesearch_body(const DevModel* __restrict__ Mg,
   // Decided here, not by comparing merits, because the base merit below comes from the
   // linearisation and rounds differently from the candidate evaluation.
   bool zero_step;
-  if constexpr (W == 1 && I7M_LS_WSYNC) {
+  if constexpr (W == 1) {
     zero_step = __ballot(step_nz) == 0;
     ls_sync<W>();
   } else {
@@ -434,7 +421,6 @@ __device__ __forceinline__ void linesearch_body(const DevModel* __restrict__ Mg,
   int found = zero_step ? 1 : -1;
   const int c_end = sp.c_end < 1 + NALPHA ? sp.c_end : 1 + NALPHA;
   for (int c0 = cstart; c0 < c_end && found < 0; c0 += R * W) {
-    if (I7M_PRIO & 2) set_prio((c0 - cstart) / (R * W));  // later rounds first: the longest searches
     const int cw = c0 + w * R;  // this wave's first candidate of the round
     const int cand = cw + slot;
     const LsKernArgs* KR = KA ? kernarg_ls() : nullptr;
@@ -447,20 +433,8 @@ __device__ __forceinline__ void linesearch_body(const DevModel* __restrict__ Mg,
       // XU / sol where they are used instead of being held in registers across the dynamics
       // (the line-search point XU + al (sol - XU), src/osqp_sqp.py:60)
       const bool last = (k == N - 1);
-      const bool base_pt = (cand == 0);
-      const double al = base_pt ? 0.0 : alphas[cand - 1];
-      const int ok = 18 * k, on = 18 * (last ? k : k + 1);
-      auto val = [&](int e) -> double {
-        const XD p = sXD[e];
-        const double v = p.x + al * p.d;
-        return ls_pick(base_pt, p.x, v);
-      };
-      if (ABL == 1) {  // diagnostic timing build: dynamics replaced by trivial math
-        o[0] = val(ok) * val(ok + 1); o[1] = val(ok + 6) * val(ok + 6); o[2] = val(ok + 12) * val(on);
-        o[3] = val(on + 6) + val(ok + 11);
-      } else {
-        ls_merit_terms<SPEC, FW>(Mg, PR, k, last, base_pt, al, sXD, goal, f6r, fpark + l, o);
-      }
+      const double al = (cand == 0) ? 0.0 : alphas[cand - 1];
+      ls_merit_terms<SPEC, FW>(Mg, PR, k, last, al, sXD, goal, f6r, fpark + l, o);
       if (k == 0 && cand > 0) {
         // + |XU_new[:12] - XU[:12]|   (src/osqp_sqp.py:63)
         double dd = 0.0;
@@ -470,8 +444,7 @@ __device__ __forceinline__ void linesearch_body(const DevModel* __restrict__ Mg,
         __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
         for (int i = 0; i < 12; ++i) {
-          const double vi = p0[i].x + al * p0[i].d;
-          const double t = ls_pick(base_pt, p0[i].x, vi) - p0[i].x;
+          const double t = (p0[i].x + al * p0[i].d) - p0[i].x;
           dd += t * t;
         }
         o[3] += sqrt(dd);
@@ -547,14 +520,10 @@ __device__ __forceinline__ void linesearch_body(const DevModel* __restrict__ Mg,
   }
 }
 
-#ifndef I7M_LS_WPE
-#define I7M_LS_WPE 2  // waves per SIMD the line search is compiled for (A/B builds: 3)
-#endif
-#ifndef I7M_LS_KARG
-#define I7M_LS_KARG 1  // k_linesearch re-reads its parameters from the kernarg segment (LsKernArgs)
-#endif
-template <bool SPEC, int ABL = 0, int W = 1, bool FW = false>
-__global__ void __launch_bounds__(64 * W) __attribute__((amdgpu_waves_per_eu(I7M_LS_WPE, I7M_LS_WPE))) k_linesearch(const DevModel* __restrict__ Mg, SolveParams P,
+constexpr int LS_WPE = 2;  // waves per SIMD the line search is compiled for (3 was tried)
+// k_linesearch re-reads its parameters from the kernarg segment (LsKernArgs): KA = true
+template <bool SPEC, int W = 1, bool FW = false>
+__global__ void __launch_bounds__(64 * W) __attribute__((amdgpu_waves_per_eu(LS_WPE, LS_WPE))) k_linesearch(const DevModel* __restrict__ Mg, SolveParams P,
                                                    const double* xu, double* xu_out, const double* __restrict__ sol,
                                                    const double* __restrict__ goals, const double* __restrict__ fext,
                                                    int* __restrict__ active,
@@ -569,9 +538,9 @@ __global__ void __launch_bounds__(64 * W) __attribute__((amdgpu_waves_per_eu(I7M
   if (sp.c_begin > 0 && !sp.pending[b]) return;
   extern __shared__ __attribute__((aligned(16))) double ls_dyn[];
   __shared__ double merit[9];
-  linesearch_body<SPEC, ABL, W, FW, I7M_LS_KARG != 0>(Mg, P, b, W > 1 ? (int)(threadIdx.x >> 6) : 0, threadIdx.x & 63,
-                                                      ls_dyn, merit, xu, xu_out, sol, goals, fext, active, stats,
-                                                      alpha_out, iter, mode, lin, cost, sp);
+  linesearch_body<SPEC, W, FW, true>(Mg, P, b, W > 1 ? (int)(threadIdx.x >> 6) : 0, threadIdx.x & 63,
+                                     ls_dyn, merit, xu, xu_out, sol, goals, fext, active, stats, alpha_out, iter, mode,
+                                     lin, cost, sp);
 }
 
 // Merit pieces of a given XU (hooks for SQP_OSQP.eepos_cost / integrator_err).

@@ -34,24 +34,13 @@ namespace i7m {
 constexpr int KPW = 10;   // knots per wavefront
 constexpr int XS = 20;    // LDS doubles per link slot (round 1 uses 19)
 
-// Where the 6x6 factor of M lives: 0 = every lane's registers (chol6; default), 1 = LDS,
-// factorised by the knot's six lanes together (21 doubles fewer per lane).  Measured on
-// MI355X at B = 4096: registers 96.1 us, LDS 99.7 us per launch.
-#ifndef I7M_LIN_CHOL_LDS
-#define I7M_LIN_CHOL_LDS 0
-#endif
-
-// Occupancy target of k_linearize (amdgpu_waves_per_eu): 0 = the compiler's choice (242 VGPRs,
-// 2 waves per SIMD; default).  3 caps it at 168 VGPRs (its 12.7 KB of LDS allows 3 waves) and
+// The 6x6 factor of M lives in every lane's registers (chol6).  In LDS, factorised by the knot's
+// six lanes together (21 doubles fewer per lane), it measured slower on MI355X at B = 4096
+// (DESIGN.md §4.1): registers 96.1 us, LDS 99.7 us per launch.
+//
+// k_linearize's occupancy is the compiler's choice (242 VGPRs, 2 waves per SIMD).  An
+// amdgpu_waves_per_eu of 3 caps it at 168 VGPRs (its 12.7 KB of LDS allows 3 waves) and
 // spills 21-42 VGPRs: 105-118 us against 96 us.
-#ifndef I7M_LIN_WPE
-#define I7M_LIN_WPE 0
-#endif
-#if I7M_LIN_WPE > 0
-#define I7M_LIN_OCC __attribute__((amdgpu_waves_per_eu(I7M_LIN_WPE, I7M_LIN_WPE)))
-#else
-#define I7M_LIN_OCC
-#endif
 
 // spatial helpers on 6-vectors [lin; ang]
 __device__ __forceinline__ void mcross(const double* a, const double* b, double* o) {  // a x b (motion)
@@ -83,25 +72,6 @@ __device__ __forceinline__ void imul(double m, const double* h, const double* I,
   o[5] = kadd(kdot3(I[2], x[3], I[4], x[4], I[5], x[5]), kmsub(kmul(h[0], x[1]), h[1], x[0]));
 }
 
-// Solve L L^T x = b in place, L from chol6's layout (strict lower triangle = L, diagonal =
-// 1 / L_jj), row-major 6x6 in LDS, read entry by entry (the operation order of chol6_solve).
-__device__ __forceinline__ void chol6_solve_lds(const double* Lm, double b[6]) {
-#pragma unroll
-  for (int i = 0; i < 6; ++i) {
-    double v = b[i];
-#pragma unroll
-    for (int k = 0; k < i; ++k) v -= Lm[6 * i + k] * b[k];
-    b[i] = v * Lm[6 * i + i];
-  }
-#pragma unroll
-  for (int i = 5; i >= 0; --i) {
-    double v = b[i];
-#pragma unroll
-    for (int k = i + 1; k < 6; ++k) v -= Lm[6 * k + i] * b[k];
-    b[i] = v * Lm[6 * i + i];
-  }
-}
-
 // Padding after each knot's six link slots (doubles).  The lanes of a knot read the same slot
 // (a broadcast) while the knots of a ds_read_b128 lane group read different ones, so the knot
 // stride decides the bank conflicts: unpadded (120 doubles = 240 dwords, 48 mod 64 banks) knots
@@ -109,14 +79,10 @@ __device__ __forceinline__ void chol6_solve_lds(const double* Lm, double b[6]) {
 // extra cycles per LDS instruction); 124 doubles (56 mod 64) give every knot of each lane group
 // ({0,2,3,4}, {0..5}, {5,7,8,9}, {6,7,8} + the idle lanes, which read knot KPW - 1) its own
 // four banks.
-#ifndef I7M_LIN_XPAD
-#define I7M_LIN_XPAD 4
-#endif
+constexpr int LIN_XPAD = 4;
 struct alignas(16) KnotSlots {
   double s[6][XS];
-#if I7M_LIN_XPAD > 0
-  double pad[I7M_LIN_XPAD];
-#endif
+  double pad[LIN_XPAD];
   __device__ __forceinline__ double* operator[](int i) { return s[i]; }
 };
 // LDS of one wave's linearisation pass (KPW knots): per-link exchange slots, M, RNEA bias.  16-byte
@@ -454,41 +420,6 @@ __device__ __forceinline__ void linearize_body(const DevModel* __restrict__ Mg, 
   }
   wave_sync();
 
-#if I7M_LIN_CHOL_LDS
-  // ---- 4. M = L L^T, factorised by the knot's six lanes together (lane r holds row r; column c
-  // is closed by lane c, then by the lanes r > c, the finished rows passing through sM).  Same
-  // operation order as chol6, so the same factor; it overwrites M in sM and stays there for
-  // the solves (chol6_solve_lds): no lane holds the whole factor in registers.
-  {
-    double Lr[6];
-#pragma unroll
-    for (int cc = 0; cc < 6; ++cc) Lr[cc] = sM[gg][6 * j + cc];
-    wave_sync();  // every lane has read its row of M
-#pragma unroll
-    for (int c = 0; c < 6; ++c) {
-      if (j == c) {
-        double d = Lr[c];
-#pragma unroll
-        for (int kk = 0; kk < c; ++kk) d -= Lr[kk] * Lr[kk];
-        Lr[c] = rsqrt_nr(d);
-        if (g < KPW) {
-#pragma unroll
-          for (int kk = 0; kk <= c; ++kk) sM[gg][6 * c + kk] = Lr[kk];
-        }
-      }
-      wave_sync();
-      if (j > c) {
-        const double* Lc = &sM[gg][6 * c];
-        double v = Lr[c];
-#pragma unroll
-        for (int kk = 0; kk < c; ++kk) v -= Lr[kk] * Lc[kk];
-        Lr[c] = v * Lc[c];
-      }
-    }
-  }
-  const double* Lm = &sM[gg][0];
-  auto lsolve = [&](double* x) { chol6_solve_lds(Lm, x); };
-#else
   // ---- 4. M = L L^T in every lane's registers (chol6)
   double L[6][6];
 #pragma unroll
@@ -497,7 +428,6 @@ __device__ __forceinline__ void linearize_body(const DevModel* __restrict__ Mg, 
     for (int cc = 0; cc < 6; ++cc) L[r][cc] = sM[gg][6 * r + cc];
   chol6(L);
   auto lsolve = [&](double* x) { chol6_solve(L, x); };
-#endif
   // a = M^-1 (u - tau0) (every lane), dA_j = sum_{i<=j} S_i a_i, g_j = I_j dA_j,
   // Fs_j = sum_{i>=j} g_i; then with sd = S_j x dA_j (Z_j = Zp_j + sd, y_j = yp_j + S_j x* Fs_j
   // - IC_j sd):  dq_r += -a_r . sd (r >= j),  S_r . (S_j x* Fs_j - IC_j sd) (r < j)
@@ -621,7 +551,7 @@ __device__ __forceinline__ void linearize_body(const DevModel* __restrict__ Mg, 
 
 // KPW consecutive knots of the flattened (problem, knot) index per 64-lane wave.
 template <bool SPEC, bool FW = false>
-__global__ void __launch_bounds__(64) I7M_LIN_OCC k_linearize(const DevModel* __restrict__ Mg, SolveParams P,
+__global__ void __launch_bounds__(64) k_linearize(const DevModel* __restrict__ Mg, SolveParams P,
                                                   const double* __restrict__ xu, const double* __restrict__ goals,
                                                   const double* __restrict__ fext, const int* __restrict__ active,
                                                   double* __restrict__ lin, double* __restrict__ cost,

@@ -139,6 +139,28 @@ inline bool tuning_from_env(const i7m_config& cfg, Tuning* t, std::string* err) 
   return true;
 }
 
+// An I7M_ABLATE value of the diagnostic (-DI7M_DIAG) library: one a kernel acts on, one whose
+// timing variant was retired with the Riccati and line-search ablations (DESIGN.md §7 has their
+// numbers; commit a2cf0e7 is the last tree that builds them), or one no kernel ever looked at.
+// `msg` is null for a known value.  i7m_create refuses the other two, so that an old script does
+// not silently time the default.
+enum class Ablate { known, retired, unknown };
+struct AblateStatus {
+  Ablate kind;
+  const char* msg;
+};
+inline AblateStatus ablate_status(int v) {
+  // known: 0 none; 21 the OSQP sweep without its stream (i7m_admm_iter.h); 40..44 k_ipm_fused's
+  // fixed iteration count and skipped parts (i7m_box.h); 100000 + 100 IT + S, 200000 + K,
+  // 300000 + P the stamps of the OSQP iteration, the factor and the scaling (tools/step_stamps.py)
+  if (v == 0 || v == 21 || (v >= 40 && v <= 44) || v >= 100000) return {Ablate::known, nullptr};
+  for (int r : {1, 2, 4, 6, 8, 10, 11, 13, 18, 19})
+    if (v == r)
+      return {Ablate::retired, "I7M_ABLATE names a Riccati / line-search timing variant that was retired (DESIGN.md "
+                               "§7 has its numbers; commit a2cf0e7 is the last tree that builds it): unset it"};
+  return {Ablate::unknown, "I7M_ABLATE is set to a value that no kernel acts on: unset it"};
+}
+
 // ---- selectors: Tuning and sizes in, the decision out -------------------------------------------
 
 // The OSQP iteration kernel of a launch of n problems at horizon N: k_admm_iter<true> (rho

@@ -7,8 +7,8 @@
 //     A~ = [[A, c], [0, 1]],  B~ = [B; 0],  Q~ = [[Q, q], [q', 0]],  N~ = [0 | r]
 //     W0 = V~ A~,  Qxx = A~' W0 + Q~,  W1 = V~ B~,  H = B~' W1 + R,  G~ = B~' W0 + N~
 //     K~ = -H^-1 G~  (6x13: [K | kff]),   V~ <- Qxx + K~' G~
-// (First form: sixteen 16x16x4 MFMAs per stage; now 7 of them and 8 4x4x4_4b, I7M_RIC_44 and
-// I7M_QXX_K0_VALU below.)  V~ never leaves the accumulator registers: it is
+// (First form: sixteen 16x16x4 MFMAs per stage; now 7 of them and 8 4x4x4_4b: the 4x4-block
+// products and Qxx's VALU k-step below.)  V~ never leaves the accumulator registers: it is
 // symmetric, so the C/D layout of V~ (lane holds V[(l>>4)+4i][l&15]) is exactly the A-operand
 // layout (V[l&15][4s+(l>>4)]) the next stage needs.  Likewise W0 / W1 / G~ are consumed as
 // B operands straight from their accumulators.  LDS only carries the stage data, H and G~
@@ -17,13 +17,11 @@
 //     A[row=l&15][k=l>>4], B[k=l>>4][col=l&15], D[row=(l>>4)+4i][col=l&15], i=0..3.
 #pragma once
 
-#ifndef I7M_RIC_FD
-#define I7M_RIC_FD 2  // forward-rollout prefetch depth (stages)
-#endif
-
 #include "i7m_kernels.h"
 
 namespace i7m {
+
+constexpr int RIC_FD = 2;  // forward-rollout prefetch depth (stages)
 
 typedef double d4 __attribute__((ext_vector_type(4)));
 
@@ -46,9 +44,8 @@ enum : int {
   MO_KT = 290,   // 78  K~ (6 x 13)
   MO_ZERO = 368,
   MO_ONE = 369,
-  MO_GJ = 370,   // 6 x 40  per-pivot Gauss-Jordan exchange slots (diagnostic variant)
-  MO_DUMMY = MO_GJ,  // 64: lane l's sink for the stores it has nothing to write (branch-free)
-  // 4x4-block products (S44): V~'s v-v block, W = V_vv Bu, W0's v rows (all 6 x 6 / 6 x 13 row-major)
+  MO_DUMMY = 370,  // 64: lane l's sink for the stores it has nothing to write (branch-free)
+  // 4x4-block products: V~'s v-v block, W = V_vv Bu, W0's v rows (all 6 x 6 / 6 x 13 row-major)
   MO_VV = 610,
   MO_WV = 646,
   MO_W0V = 682,
@@ -58,29 +55,20 @@ enum : int {
   MO_TOTAL_W2 = 1018,
 };
 
-// I7M_RIC_44 (default 1): the stage's small products — H = Bu V_vv Bu + R and G~ = Bu W0_v + N~
-// — on v_mfma_f64_4x4x4_4b blocks instead of padded 16x16x4 MFMAs.  On gfx950
+// The stage's small products — H = Bu V_vv Bu + R and G~ = Bu W0_v + N~ — run on
+// v_mfma_f64_4x4x4_4b blocks instead of padded 16x16x4 MFMAs.  On gfx950
 // fp64 MFMA and fp64 VALU share one rate, and the 4x4x4_4b form retires FMAs at the 16x16x4 rate
 // (tools/probes/fp64_pipes.hip), so an MFMA costs its padded size: H's two 16x16x4 steps (128
 // cycles) did 216 useful FMAs of 2048, W1 = V B~ and G~ 23 % each.  As blocks: W (2 instructions),
 // H (2), G~ (4) = 128 cycles for what took 384.  Bit-identical to the 16x16 form: both MFMAs
 // accumulate their k-steps as an fma chain in k order and the padding adds exact zeros
-// (tools/lib_diff.py, -DI7M_RIC_44=0 against the default: 0 of 4096 config-3 problems, 0 of 256
+// (tools/lib_diff.py against the 16x16 build: 0 of 4096 config-3 problems, 0 of 256
 // config-4 problems and none of the 500 closed-loop steps differ in any bit).  The two-wave
 // kernel (B <= 128) keeps the 16x16 forms: there G~ feeds wave 0's elimination straight from
 // the accumulators, and the 4x4 blocks would put an LDS round trip on that chain (+2 us per launch
 // at B <= 64).
-#ifndef I7M_RIC_44
-#define I7M_RIC_44 1
-#endif
-// I7M_QXX_K0_VALU (default 1): Qxx's k-step over A~'s q rows 0..3 as VALU adds / fmas and a lane-half
-// swap instead of a 16x16x4 MFMA (one-wave body); bit-identical (one nonzero term per entry).
-#ifndef I7M_QXX_K0_VALU
-#define I7M_QXX_K0_VALU 1
-#endif
-#ifndef I7M_RIC_VV_PLAIN
-#define I7M_RIC_VV_PLAIN 0
-#endif
+// Qxx's k-step over A~'s q rows 0..3 is VALU adds / fmas and a lane-half swap instead of a
+// 16x16x4 MFMA (one-wave body); bit-identical (one nonzero term per entry).
 // I7M_RIC_44X (default 0, an A/B build): Qxx's v-row k-steps and V~'s update on
 // 4x4x4_4b blocks without the homogeneous row block.  A 4x4x4_4b instruction whose B operand is a 16x16x4 B operand
 // (the layouts coincide) and whose A operand replicates one row block rb of the left factor over
@@ -94,6 +82,9 @@ enum : int {
 // twelve A-operand LDS reads per stage (the 16x16 form reads two and reuses A~'s B-operand registers
 // as Qxx's A operand), their map registers (4 VGPRs spilled at the 128 cap) and unpacking cost more
 // than the 64 fp64-pipe cycles the row blocks save.
+// (The one build-time switch left: without its operand maps below, unused as they are in the
+// default build, the compiler orders every Riccati kernel's loop-invariant code differently, and
+// k_ipm_fused and k_sqp_fused come out with other instructions than the measured ones.)
 #ifndef I7M_RIC_44X
 #define I7M_RIC_44X 0
 #endif
@@ -182,24 +173,15 @@ __device__ __forceinline__ Ric44Maps ric44_maps(const int l) {
   // only to the accuracy of K~ = -H^-1 G~, and H can be very ill-conditioned (R = 1e-5 w against
   // Bu' V Bu), so H = Bu' (V~')_vv Bu keeps the recursion on the one matrix V~' throughout — with
   // V~_vv instead, 1e-8 relative errors at N = 32 and 1e-4 at N = 64 (measured).
-  // (-DI7M_RIC_VV_PLAIN=1, a test build only: V~_vv un-transposed, the recursion that loses accuracy
-  // — tests/test_gpu_riccati_value.py fails on it)
-#if I7M_RIC_VV_PLAIN
-  M.vvS = pk16((lq >= 2 && lr >= 6 && lr < 12) ? MO_VV + 6 * (lq - 2) + (lr - 6) : sink,
-               (lr >= 6 && lr < 12) ? MO_VV + 6 * (lq + 2) + (lr - 6) : sink);
-#else
+  // (tests/test_gpu_riccati_value.py fails on the un-transposed form)
   M.vvS = pk16((lq >= 2 && lr >= 6 && lr < 12) ? MO_VV + 6 * (lr - 6) + (lq - 2) : sink,
                (lr >= 6 && lr < 12) ? MO_VV + 6 * (lr - 6) + (lq + 2) : sink);
-#endif
   M.w0S = pk16((lq >= 2 && lr < 13) ? MO_W0V + 13 * (lq - 2) + lr : sink, (lr < 13) ? MO_W0V + 13 * (lq + 2) + lr : sink);
   return M;
 }
 // Laundered in the box body only (k_ipm_fused: 69 -> 24 VGPRs spilled).  The plain QP has the
 // registers for the hoisted unpacked maps (122 VGPRs), and unpacking at every use cost it ~6 %
-// (k_riccati_mfma 254 -> 270 us at B = 4096, N = 64); I7M_RIC44_LAUNDER_ALL=1 launders there too (A/B).
-#ifndef I7M_RIC44_LAUNDER_ALL
-#define I7M_RIC44_LAUNDER_ALL 0
-#endif
+// (k_riccati_mfma 254 -> 270 us at B = 4096, N = 64).
 __device__ __forceinline__ void ric44_launder(Ric44Maps& M) {
   asm volatile("" : "+v"(M.wAB[0]), "+v"(M.wAB[1]), "+v"(M.hAB[0]), "+v"(M.hAB[1]), "+v"(M.hDR), "+v"(M.wDhR2),
                "+v"(M.gA[0]), "+v"(M.gA[1]), "+v"(M.gB), "+v"(M.gD), "+v"(M.gN), "+v"(M.gN2), "+v"(M.oGB), "+v"(M.vvS),
@@ -296,26 +278,16 @@ __device__ __forceinline__ double row_shl6_f64(double v) {
 }
 
 // 1/d: v_rcp_f64 (about half the fp64 mantissa) + Newton steps, each doubling the correct
-// bits (I7M_RCP_NR, default 1: within ~2 ulp; 2 were used before, 1 is off the pivot chain of
+// bits (RCP_NR = 1: within ~2 ulp; 2 were used before, 1 is off the pivot chain of
 // every Gauss-Jordan step).
-#ifndef I7M_RCP_NR
-#define I7M_RCP_NR 1
-#endif
+constexpr int RCP_NR = 1;
 __device__ __forceinline__ double rcp_nr(double d) {
   double y = __builtin_amdgcn_rcp(d);
 #pragma unroll
-  for (int i = 0; i < I7M_RCP_NR; ++i) y = fma(y, fma(-d, y, 1.0), y);
+  for (int i = 0; i < RCP_NR; ++i) y = fma(y, fma(-d, y, 1.0), y);
   return y;
 }
 
-// ABL (diagnostic builds only, results invalid; I7M_ABLATE in i7m_api.hip maps onto them):
-// bit 0 skips the forward rollout, bit 2 selects the LDS-exchange Gauss-Jordan (bit 1 then
-// replaces it by a scaling), bit 3 sends every stage's kbuf traffic to stage 0's slot
-// (cache-resident), bit 4 the rollout's lin re-reads likewise, bit 5 drops the rollout's
-// stores (the compiler then drops the rollout's arithmetic), bit 6 feeds x instead of u to the
-// rollout's B u term (shorter chain), bit 7 skips the rollout's LDS staging, bit 8 keeps only
-// the last stage's stores, bit 9 writes per-stage phase timestamps (s_memtime) of problem 0
-// into sol (tools/ric_phases.py); used to split the kernel's time.
 // BOX: the interior-point Newton step of the box-constrained QP (oracle/box_ipm.py): the same
 // QP with Hessian P + diag(Sigma) and linear term g + h, Sigma and h given per variable in
 // bsig / bh (B, T).  The equality rows are unchanged, so the result is the Newton iterate
@@ -331,30 +303,22 @@ __device__ __forceinline__ double rcp_nr(double d) {
 // progress (ric_prio_back / _fwd), for launches with several waves per SIMD.  Measured (DESIGN.md
 // §4.2): bit 1 helps at every batch size; bit 0 cost ~4.5 us per launch at B <= 256 (a longer
 // pivot chain) until the round-3 stage changes, and helps at every batch size since, in the
-// config-4 body (BOX, k_ipm_fused, I7M_IPM_BC) too.
-#ifndef I7M_RIC_PRIO_S
-#define I7M_RIC_PRIO_S 1  // 0: quarters of the backward sweep (A/B: 113.8 vs 112.8 us at B = 4096)
-#endif
+// config-4 body (BOX, k_ipm_fused, IPM_BC) too.
 // Wave priority by progress (BC bit 2, several waves per SIMD): every problem is the same amount
 // of work, and the SIMD's oldest-first arbitration otherwise lets the first wave run ahead while
 // the youngest finishes alone at the end.  Priority falls as a wave advances, so the waves
 // behind are issued first and the four waves of a SIMD finish together.  Backward stage k of
-// N - 1 (k counts down) and forward stage k of the rollout; the default scheme keeps the lowest
+// N - 1 (k counts down) and forward stage k of the rollout; the scheme keeps the lowest
 // level short (the second half of the rollout), since the lead a wave takes there is never
-// corrected:
-__device__ __forceinline__ int ric_prio_back(int k, int N) {
-  if (I7M_RIC_PRIO_S == 1) return 2 * k >= N - 1 ? 3 : (4 * k >= N - 1 ? 2 : 1);
-  return (4 * k) / (N - 1);  // 3 .. 0 in quarters of the backward sweep; the rollout at 0
-}
-__device__ __forceinline__ int ric_prio_fwd(int k, int N) {
-  if (I7M_RIC_PRIO_S == 1) return 2 * k < N - 1 ? 1 : 0;
-  return 0;
-}
+// corrected (3 .. 0 in quarters of the backward sweep with the rollout at 0 measured 113.8
+// against 112.8 us at B = 4096):
+__device__ __forceinline__ int ric_prio_back(int k, int N) { return 2 * k >= N - 1 ? 3 : (4 * k >= N - 1 ? 2 : 1); }
+__device__ __forceinline__ int ric_prio_fwd(int k, int N) { return 2 * k < N - 1 ? 1 : 0; }
 
 // The forward rollout of one problem's QP solution (lane l of its wave, `sh` the body's LDS):
 // x_0 = xs; u_k = K~ [x_k; 1]; x_{k+1} = A x + B u + c, from the gains the backward sweep stored
 // in kbuf (K~, c_v) and the dynamics in lin; writes the minimiser to sol.
-template <int ABL, int BC>
+template <int BC>
 __device__ __forceinline__ void riccati_rollout(const int b, const SolveParams& P, const double* __restrict__ xs,
                                                 const double* __restrict__ LINb, const double* __restrict__ KB,
                                                 double* __restrict__ sol, double* __restrict__ sh, const int l) {
@@ -374,10 +338,10 @@ __device__ __forceinline__ void riccati_rollout(const int b, const SolveParams& 
   // stage element e of stage k lives at base + k * stride (resolved once per lane)
   auto fbase = [&](int e, int& stride) -> const double* {
     if (e < KBUF_STRIDE) {
-      stride = (ABL & 8) ? 0 : KBUF_STRIDE;
+      stride = KBUF_STRIDE;
       return KB + e;
     }
-    stride = (ABL & 16) ? 0 : LIN_STRIDE;
+    stride = LIN_STRIDE;
     return LINb + (e - KBUF_STRIDE);
   };
   int fs0, fs1, fs2;
@@ -404,7 +368,7 @@ __device__ __forceinline__ void riccati_rollout(const int b, const SolveParams& 
   // FD prefetch buffers used in turn (the loop is unrolled by FD), each refilled FD stages
   // ahead right after it is dropped into LDS: no register rotation, whose copies made every
   // stage wait for the loads it had just issued.
-  constexpr int FD = I7M_RIC_FD;
+  constexpr int FD = RIC_FD;
   double f[FD][3];
   auto fload = [&](double* f) {
     f[0] = *fb0;
@@ -425,13 +389,8 @@ __device__ __forceinline__ void riccati_rollout(const int b, const SolveParams& 
 #pragma unroll
   for (int d = 0; d < FD; ++d) fload(f[d]);
   auto stage = [&](const int k, double* fk) {
-    if (PRIO && I7M_RIC_PRIO_S != 0) set_prio(ric_prio_fwd(k, N));
+    if (PRIO) set_prio(ric_prio_fwd(k, N));
     double r[19];
-    if (ABL & 128) {
-#pragma unroll
-      for (int j = 0; j < 19; ++j) r[j] = fk[j % 3] * (j + 1);
-      fload(fk);
-    } else {
     wave_sync();
     sh[w0] = fk[0];
     sh[w1] = fk[1];
@@ -440,7 +399,6 @@ __device__ __forceinline__ void riccati_rollout(const int b, const SolveParams& 
     wave_sync();
 #pragma unroll
     for (int j = 0; j < 19; ++j) r[j] = myb[j];
-    }
     // x (lanes 0..11, all in DPP row 0) to every lane of the row
     double X[12];
     if (BC & 2) {
@@ -455,7 +413,7 @@ __device__ __forceinline__ void riccati_rollout(const int b, const SolveParams& 
 #pragma unroll
     for (int j = 0; j < 6; ++j) { ua += r[j] * X[j]; ub += r[6 + j] * X[6 + j]; }
     const double ureg = ua + ub;
-    if (!(ABL & 32) && (!(ABL & 256) || k == N - 2) && l < 6) S[18 * k + 12 + l] = ureg;
+    if (l < 6) S[18 * k + 12 + l] = ureg;
     double U[6];
     if (BC & 2) {
       RowBcast<0, 6>::run(ureg, U);
@@ -465,12 +423,12 @@ __device__ __forceinline__ void riccati_rollout(const int b, const SolveParams& 
     }
     double vc = 0.0;
 #pragma unroll
-    for (int j = 0; j < 6; ++j) vc += r[13 + j] * ((ABL & 64) ? X[j] : U[j]);
+    for (int j = 0; j < 6; ++j) vc += r[13 + j] * U[j];
     // q lanes: q + dt v, v_l = x_{6+l} from lane l + 6 (DPP row shift, same 16-lane row)
     const double vq = row_shl6_f64(xreg);
     const double nx = (l < 6) ? xreg + dt * vq : ureg + vc;
     xreg = nx;
-    if (!(ABL & 32) && (!(ABL & 256) || k == N - 2) && l < 12) S[18 * (k + 1) + l] = nx;
+    if (l < 12) S[18 * (k + 1) + l] = nx;
   };
   // all FD stages unconditional inside the loop (the tail after it): a path that skips a stage
   // and loops back would make the next stage wait for its own refill
@@ -491,7 +449,7 @@ __device__ __forceinline__ void riccati_rollout(const int b, const SolveParams& 
 // LDS, MO_QX).  Both waves form V~ <- Qxx + K~' G~ from the same operands (wave 1 reads G~ from
 // the elimination's LDS copy), so they hold bit-identical V~ and the result is bit-identical to
 // the one-wave body.  Three workgroup barriers per stage (stash, H / G~, K~ / Qxx).
-template <int ABL, bool BOX, bool HINV = false, int BC = 0, bool W2 = false>
+template <bool BOX, bool HINV = false, int BC = 0, bool W2 = false>
 __device__ __forceinline__ void riccati_mfma_body(const int b, const SolveParams& P, const double* __restrict__ xu,
                                                   const double* __restrict__ xs, const double* __restrict__ lin,
                                                   const double* __restrict__ cost, const double* __restrict__ qpd,
@@ -500,7 +458,7 @@ __device__ __forceinline__ void riccati_mfma_body(const int b, const SolveParams
                                                   double* __restrict__ sh, const int l,
                                                   double* __restrict__ hinv = nullptr, const bool kff_only = false,
                                                   double* __restrict__ vout = nullptr) {
-  static_assert(!W2 || (!BOX && !HINV && ABL == 0), "two-wave body: plain QP only");
+  static_assert(!W2 || (!BOX && !HINV), "two-wave body: plain QP only");
   const int lr = l & 15, lq = l >> 4;
   const int N = P.N;
   constexpr bool PRIO = (BC & 4) && !BOX && !W2;
@@ -530,7 +488,7 @@ __device__ __forceinline__ void riccati_mfma_body(const int b, const SolveParams
     }
   }
   auto opA = [&](int s) -> double { return s == 0 ? cA0 : sh[offA[s]]; };
-  // B~[4s+lq][lr] for s = 1, 2
+  // B~[4s+lq][lr] for s = 1, 2 (the two-wave body's 16x16 products)
   int offB[2];
 #pragma unroll
   for (int s = 1; s < 3; ++s) {
@@ -538,9 +496,10 @@ __device__ __forceinline__ void riccati_mfma_body(const int b, const SolveParams
     offB[s - 1] = (k >= 6 && lr < 6) ? MO_BU + 6 * (k - 6) + lr : MO_ZERO;
   }
   // Q~[lq+4i][lr] = sh[q1[i]] * sh[q2[i]]: rank-1 (Qm j) j' q block, dQm on the v diagonal, the
-  // linear terms in row / column 12;  R on the u diagonal;  N~ = r in column 12.
-  // BOX adds Sigma on the diagonals and h on the linear terms (oS for Q~, oR2 / oN2 for R, N~).
-  int q1[4], q2[4], oR[4], oN[4], oS[4], oR2[4], oN2[4];
+  // linear terms in row / column 12;  R on the u diagonal;  N~ = r in column 12 (oR, oN: the
+  // two-wave body's 16x16 products).
+  // BOX adds Sigma on the diagonals and h on the linear terms (oS for Q~; Ric44Maps for R, N~).
+  int q1[4], q2[4], oR[4], oN[4], oS[4];
 #pragma unroll
   for (int i = 0; i < 4; ++i) {
     const int r = lq + 4 * i, c = lr;
@@ -558,8 +517,6 @@ __device__ __forceinline__ void riccati_mfma_body(const int b, const SolveParams
       else if (r < 12 && c == 12) oS[i] = MO_HB + r;
       else if (r == 12 && c < 12) oS[i] = MO_HB + c;
     }
-    oR2[i] = (BOX && r == c && r < 6) ? MO_SIG + 12 + r : MO_ZERO;
-    oN2[i] = (BOX && c == 12 && r < 6) ? MO_HB + 12 + r : MO_ZERO;
   }
   const double m12 = (lr == 12) ? 1.0 : 0.0, mlq0 = (lq == 0) ? 1.0 : 0.0;
   const double mdt_hi = (lq >= 2) ? dt : 0.0, mdt_lo = (lq < 2) ? dt : 0.0;
@@ -571,14 +528,13 @@ __device__ __forceinline__ void riccati_mfma_body(const int b, const SolveParams
     oK[s] = (u < 6 && lr < 13) ? MO_KT + 13 * u + lr : MO_ZERO;
   }
 
-  // the small products on 4x4x4 blocks (I7M_RIC_44), the box body too (its Sigma_u / h_u join
-  // the C inputs); not the two-wave kernel (see I7M_RIC_44) nor the diagnostic LDS-exchange elimination
-  constexpr bool S44 = I7M_RIC_44 && !(ABL & 4) && !W2;
+  // the small products on 4x4x4 blocks in the one-wave body, the box body too (its Sigma_u / h_u
+  // join the C inputs); the two-wave body keeps the 16x16 forms (see the top of this file)
   Ric44Maps M44 = ric44_maps<BOX>(l);
   // I7M_RIC_44X: A operands of the row-block products (lane l: k = l >> 4, row i = l & 3 of the block)
   //   Qxx: A~'[4rb + i][4ks + k] = A~[4ks + k][4rb + i], k-steps ks = 1, 2 (packed lo | hi)
   //   V~ : K~'[4rb + i][4ks + k] = K~[4ks + k][4rb + i], k-steps ks = 0, 1
-  constexpr bool X44 = I7M_RIC_44X && S44;
+  constexpr bool X44 = I7M_RIC_44X && !W2;
   unsigned qxA[3], vxA[3];
 #pragma unroll
   for (int rb = 0; rb < 3; ++rb) {
@@ -657,24 +613,14 @@ __device__ __forceinline__ void riccati_mfma_body(const int b, const SolveParams
 #pragma unroll
   for (int i = 0; i < 4; ++i) V[i] = BOX ? sh[q1[i]] * sh[q2[i]] + sh[oS[i]] : sh[q1[i]] * sh[q2[i]];
 
-  // ABL bit 9 (diagnostic): per-stage phase timestamps (s_memtime) of problem 0 into sol
-  long long tm0 = 0, tm1 = 0, tm2 = 0, tm3 = 0, ta = 0, tb = 0, td = 0, te = 0, tp = 0;
-  auto tstamp = [](double dep) -> long long {
-    asm volatile("" ::"v"(dep));
-    return (long long)__builtin_amdgcn_s_memtime();
-  };
   for (int k = N - 2; k >= 0; --k) {
-    if constexpr (S44 && (BOX || I7M_RIC44_LAUNDER_ALL)) ric44_launder(M44);
+    if constexpr (BOX) ric44_launder(M44);
     if constexpr (W2) {
       lds_sync();  // every wave is done with the previous stage's LDS
       if (w == 0) {
         sh[MO_AQ + l] = p0;
         sh[MO_AQ + l + 64] = p1;
         sh[l + 128 < SE ? MO_AQ + l + 128 : MO_DUMMY + l] = p2;
-        if constexpr (S44) {
-          sh[lo16(M44.vvS)] = V[1];
-          sh[hi16(M44.vvS)] = V[2];
-        }
       }
       lds_sync();
       if (w == 0 && k > 0) stash_next();
@@ -689,12 +635,6 @@ __device__ __forceinline__ void riccati_mfma_body(const int b, const SolveParams
         for (int i = 0; i < 4; ++i) W0[i] = (lr == 12) ? V[i] : 0.0;
 #pragma unroll
         for (int s = 0; s < 3; ++s) W0 = mfma(V[s], bA[s], W0);
-        if constexpr (S44) {
-          sh[lo16(M44.w0S)] = W0[1];
-          sh[hi16(M44.w0S)] = W0[2];
-          wave_sync();
-          ric44_g<BOX>(M44, sh);
-        } else {
         d4 Ni;
 #pragma unroll
         for (int i = 0; i < 4; ++i) Ni[i] = sh[oN[i]];
@@ -705,9 +645,6 @@ __device__ __forceinline__ void riccati_mfma_body(const int b, const SolveParams
           const int r = lq + 4 * i;
           sh[(r < 6 && lr < 13) ? MO_G + 13 * r + lr : MO_DUMMY + l] = Z10[i];
         }
-        }
-      } else if (S44) {
-        ric44_h<BOX>(M44, sh);
       } else {
         d4 Ri;
 #pragma unroll
@@ -766,9 +703,8 @@ __device__ __forceinline__ void riccati_mfma_body(const int b, const SolveParams
 #pragma unroll
         for (int i = 0; i < 4; ++i) Z00[i] = sh[MO_QX + 64 * i + l];
       }
-      if (w != 0 || S44) {
-        // G~ as wave 0's accumulators held it (rows >= 6 and columns >= 13 are exact zeros there);
-        // S44: both waves (G~ came from 4x4 blocks, not from a 16x16 accumulator)
+      if (w != 0) {
+        // G~ as wave 0's accumulators held it (rows >= 6 and columns >= 13 are exact zeros there)
 #pragma unroll
         for (int i = 0; i < 2; ++i) {
           const int r = lq + 4 * i;
@@ -786,263 +722,145 @@ __device__ __forceinline__ void riccati_mfma_body(const int b, const SolveParams
     }
     if (PRIO) set_prio(ric_prio_back(k, N));
     wave_sync();
-    if (ABL & 512) tm0 = tstamp(V[0]);
-    if (ABL & 512) tp = tstamp(p0 + p1 + p2);
     sh[MO_AQ + l] = p0;
     sh[MO_AQ + l + 64] = p1;
     if (BF) sh[l + 128 < SE ? MO_AQ + l + 128 : MO_DUMMY + l] = p2;
     else if (l + 128 < SE) sh[MO_AQ + l + 128] = p2;
-    if constexpr (S44) {  // V~'s v-v block for H = Bu' V_vv Bu (4x4 blocks)
-      sh[lo16(M44.vvS)] = V[1];
-      sh[hi16(M44.vvS)] = V[2];
-    }
+    // V~'s v-v block for H = Bu' V_vv Bu (4x4 blocks)
+    sh[lo16(M44.vvS)] = V[1];
+    sh[hi16(M44.vvS)] = V[2];
     wave_sync();
     if (k > 0) stash_next();
-    double bA[3], bB[2];
+    double bA[3];
 #pragma unroll
     for (int s = 0; s < 3; ++s) bA[s] = opA(s);
-    d4 Qi, Ri, Ni;
+    d4 Qi;
 #pragma unroll
     for (int i = 0; i < 4; ++i)
       // (x + 0.0 is not folded for doubles: the box shifts are added only in BOX builds)
       // (rows >= 8 — registers 2, 3 — hold no rank-1 entries: their second factor is 1 or the
       // first is 0, so the product is the first factor itself)
       Qi[i] = BOX ? (i < 2 ? sh[q1[i]] * sh[q2[i]] : sh[q1[i]]) + sh[oS[i]] : (i < 2 ? sh[q1[i]] * sh[q2[i]] : sh[q1[i]]);
-    if constexpr (!S44) {
-      bB[0] = sh[offB[0]];
-      bB[1] = sh[offB[1]];
-#pragma unroll
-      for (int i = 0; i < 4; ++i) {
-        Ri[i] = BOX ? sh[oR[i]] + sh[oR2[i]] : sh[oR[i]];
-        Ni[i] = BOX ? sh[oN[i]] + sh[oN2[i]] : sh[oN[i]];
-      }
-    }
     // W0 = V A~ ; Qxx = A~' W0 + Q~.  Rows 12..15 of A~ are e_12' and 0: their k-step is a
     // select (W0[:,12] += V[:,12], Qxx[12,:] += W0[12,:]) instead of an MFMA.
-    if (ABL & 512) ta = tstamp(bA[0] + bA[1] + bA[2] + bB[0] + bB[1] + Qi[0] + Ri[0] + Ni[0]);
     d4 W0;
     // (lr == 12 ? V : +0) as one fma per register instead of two 32-bit selects
 #pragma unroll
     for (int i = 0; i < 4; ++i) W0[i] = (X44 && i == 3) ? 0.0 : fma(V[i], m12, 0.0);
 #pragma unroll
     for (int s = 0; s < 3; ++s) W0 = mfma(V[s], bA[s], W0);
-    if (ABL & 512) tb = tstamp(W0[0] + W0[1] + W0[2] + W0[3]);
     d4 Z00 = Qi;
-    d4 Z10, Z11;
-    if constexpr (S44) {
-      // W0's v rows for G~; then H = Bu' V_vv Bu + R (under the Qxx chain), G~ = Bu' W0_v + N~,
-      // both stored into MO_H / MO_G for the elimination
-      sh[lo16(M44.w0S)] = W0[1];
-      sh[hi16(M44.w0S)] = W0[2];
-      ric44_h<BOX>(M44, sh);
-      if (!X44) Z00[3] = fma(W0[3], mlq0, Z00[3]);  // row 12's k-step: + W0[12][:] on the lanes lq == 0
-      if constexpr (I7M_QXX_K0_VALU) {
-        // k-step 0 (A~'s q rows 0..3: 1 at (k, k), dt at (k, k + 6)) on the VALU: rows 0..3 of Qxx
-        // gain W0's rows 0..3 (same lanes), rows 6..9 dt times them (the other half of the wave:
-        // one v_permlane32_swap per dword).  One nonzero term per entry, rounded as the MFMA's
-        // k-step rounds it (bit-identical).
-        // Q~'s rank-1 products stay rounded on their own, as the MFMA's C input (otherwise the
-        // compiler contracts them into the adds below)
-        asm volatile("" : "+v"(Z00[0]), "+v"(Z00[1]));
-        Z00[0] = Z00[0] + W0[0];
-        const long long wb = __double_as_longlong(W0[0]);
-        const auto slo = __builtin_amdgcn_permlane32_swap((unsigned)wb, (unsigned)wb, false, false);
-        const auto shi = __builtin_amdgcn_permlane32_swap((unsigned)(wb >> 32), (unsigned)(wb >> 32), false, false);
-        // lanes 32..63 of the first result: W0 from lanes 0..31 (rows 0, 1); lanes 0..31 of the
-        // second: from lanes 32..63 (rows 2, 3)
-        const double up = __longlong_as_double(((long long)shi[0] << 32) | (unsigned)slo[0]);
-        const double dn = __longlong_as_double(((long long)shi[1] << 32) | (unsigned)slo[1]);
-        // (an fma: the MFMA's k-step adds its exact product to C — measured: a separately rounded
-        // product changes 4 091 of 4 096 config-3 solves, the fma none)
-        Z00[1] = fma(up, mdt_hi, Z00[1]);  // rows 6, 7 (lq 2, 3)
-        Z00[2] = fma(dn, mdt_lo, Z00[2]);  // rows 8, 9 (lq 0, 1)
-        if constexpr (X44) {
-          // k-steps 1, 2 as three row blocks each (the 16x16 D registers 0..2)
-#pragma unroll
-          for (int rb = 0; rb < 3; ++rb) {
-            Z00[rb] = mfma44(sh[lo16(qxA[rb])], W0[1], Z00[rb]);
-            Z00[rb] = mfma44(sh[hi16(qxA[rb])], W0[2], Z00[rb]);
-          }
-        } else {
-#pragma unroll
-          for (int s = 1; s < 3; ++s) Z00 = mfma(bA[s], W0[s], Z00);
-        }
-      } else {
-#pragma unroll
-        for (int s = 0; s < 3; ++s) Z00 = mfma(bA[s], W0[s], Z00);
-      }
-      ric44_g<BOX>(M44, sh);
-    } else {
-    if (lq == 0) Z00[3] += W0[3];
-#pragma unroll
-    for (int s = 0; s < 3; ++s) Z00 = mfma(bA[s], W0[s], Z00);
-    // W1 = V B~ ; H = B~' W1 + R ; G~ = B~' W0 + N~   (B~ rows 6..11 only: k-steps 1, 2)
-    d4 W1 = {0.0, 0.0, 0.0, 0.0};
-    W1 = mfma(V[1], bB[0], W1);
-    W1 = mfma(V[2], bB[1], W1);
-    Z11 = mfma(bB[0], W1[1], Ri);
-    Z11 = mfma(bB[1], W1[2], Z11);
-    if (ABL & 512) tm1 = tstamp(bA[0] + bA[1] + bA[2] + Qi[0] + Ri[0] + Ni[0]);
-    Z10 = mfma(bB[0], W0[1], Ni);
-    Z10 = mfma(bB[1], W0[2], Z10);
-    if (ABL & 512) tm2 = tstamp(Z10[0] + Z10[1] + Z11[0] + Z11[1]);
-    }
-    double* kk = KB + (long)((ABL & 8) ? 0 : k) * KBUF_STRIDE;
-    if ((ABL & 4) && !BOX) {
-      // (Diagnostic alternative, I7M_ABLATE=8: measured 5 us slower per launch at B = 1 and
-      // level at B = 4096 than the column-per-lane elimination below)
-      // K~ = -H^-1 G~ by Gauss-Jordan on [H | G~] (6 x 19) in place in the MFMA accumulator
-      // layout: lane l holds column lr of rows lq and lq + 4 (lq < 2) of H (lr < 6) and of G~
-      // (lr < 13).  Pivot p needs, per lane, M[r][p] of its two rows (published by the lanes
-      // lr == p) and M[p][lr] of its column (published by the lanes lq == p & 3): a per-pivot
-      // LDS slot, two writes and three broadcast-friendly reads, instead of 12 v_readlane per
-      // pivot.  The arithmetic is the column-per-lane elimination's, operation for operation.
-      // SPD H: no pivoting.  K~ ends where the V~ update wants it: the A operand of k-step s is
-      // K~[4s + lq][lr], i.e. this lane's G~ entry of row lq + 4s.  (The box variants keep the
-      // column-per-lane form below: fewer live registers next to their Sigma / h operand maps.)
-      double eh0 = Z11[0], eh1 = Z11[1], eg0 = Z10[0], eg1 = Z10[1];
-      if (ABL & 2) {
-        eh0 *= 1e-3; eh1 *= 1e-3; eg0 *= 1e-3; eg1 *= 1e-3;
-      } else {
-#pragma unroll
-        for (int p = 0; p < 6; ++p) {
-          double* col = sh + MO_GJ + 40 * p;  // col[2 lq + i] = M[lq + 4i][p]
-          double* row = col + 8;              // row[2 lr + j] = M[p][lr] of H (j = 0), G~ (j = 1)
-          if (lr == p) {
-            col[2 * lq] = eh0;
-            col[2 * lq + 1] = eh1;
-          }
-          if (lq == (p & 3)) {
-            row[2 * lr] = (p >> 2) ? eh1 : eh0;
-            row[2 * lr + 1] = (p >> 2) ? eg1 : eg0;
-          }
-          wave_sync();
-          const double mr0 = col[2 * lq], mr1 = col[2 * lq + 1];
-          const double mph = row[2 * lr], mpg = row[2 * lr + 1];
-          const double inv = rcp_nr(row[2 * p]);
-          const double eph = mph * inv, epg = mpg * inv;
-          eh0 = (lq == p) ? eph : eh0 - mr0 * eph;
-          eg0 = (lq == p) ? epg : eg0 - mr0 * epg;
-          eh1 = (lq + 4 == p) ? eph : eh1 - mr1 * eph;
-          eg1 = (lq + 4 == p) ? epg : eg1 - mr1 * epg;
-        }
-      }
-      const double ka0 = (lr < 13) ? -eg0 : 0.0;
-      const double ka1 = (lq < 2 && lr < 13) ? -eg1 : 0.0;
-      // V~ <- Qxx + K~' G~
-      V = mfma(ka0, Z10[0], Z00);
-      V = mfma(ka1, Z10[1], V);
-      // K~ (78, row-major 6 x 13) and c_v (6) -> global for the forward rollout
-      if (lr < 13) {
-        kk[13 * lq + lr] = ka0;
-        if (lq < 2) kk[13 * (lq + 4) + lr] = ka1;
-      }
-      if (l < 6) kk[78 + l] = sh[MO_CV + l];
-    } else {
-      // Column-per-lane Gauss-Jordan (every variant by default): H, G~ through LDS, one column
-      // of [H | G~ (| I)] per lane, the pivot column broadcast by DPP row_newbcast, which stays
-      // inside a 16-lane row — so each of the two rows used carries its own copy of H's six
-      // columns: row 0 = H 0..5, G~ 0..9; row 1 = H 0..5 again, G~ 10..12 and (HINV) the
-      // identity columns, which end as H^-1.  The two copies of H evolve identically.
-      // (stores of lanes with nothing to store go to their own dummy slot: no exec-mask branches)
-      if constexpr (!S44) {
-#pragma unroll
-      for (int i = 0; i < 2; ++i) {
-        const int r = lq + 4 * i;
-        if (BF) {
-          sh[(r < 6 && lr < 6) ? MO_H + 6 * r + lr : MO_DUMMY + l] = Z11[i];
-          sh[(r < 6 && lr < 13) ? MO_G + 13 * r + lr : MO_DUMMY + l] = Z10[i];
-        } else if (r < 6) {
-          if (lr < 6) sh[MO_H + 6 * r + lr] = Z11[i];
-          if (lr < 13) sh[MO_G + 13 * r + lr] = Z10[i];
-        }
-      }
-      }
-      wave_sync();
-      if constexpr (S44) {  // G~ in the 16x16x4 B layout for V~'s update below
-        Z10[0] = sh[lo16(M44.oGB)];
-        Z10[1] = sh[hi16(M44.oGB)];
-      }
-      double E[6];
-      // column of lane l: 0..5 H, 6..18 G~, 19..24 identity (HINV); -1 unused (rows 2, 3 and
-      // row 1's tail compute a copy of H column 0 and store nothing)
-      const int m16 = l & 15;
-      const int ncol = HINV ? 25 : 19;
-      const int cc_own = !(BC & 1) ? l
-                         : (l < 16) ? m16 : (l < 32 ? (m16 < 6 ? m16 : (m16 < (HINV ? 15 : 9) ? m16 + 10 : -1)) : -1);
-      const int cc = !(BC & 1) ? (l < ncol ? l : ncol - 1) : (cc_own < 0 ? 0 : cc_own);
-      const int eo = (cc < 6) ? MO_H + cc : MO_G + (cc - 6), es = (cc < 6) ? 6 : 13;
-#pragma unroll
-      for (int i = 0; i < 6; ++i) {
-        E[i] = sh[eo + es * (HINV && cc >= 19 ? 0 : i)];
-        if (HINV && cc >= 19) E[i] = (i == cc - 19) ? 1.0 : 0.0;
-      }
-      if (ABL & 512) td = tstamp(E[0] + E[1] + E[2] + E[3] + E[4] + E[5]);
-#pragma unroll
-      for (int p = 0; p < 6; ++p) {
-        double Pc[6];
-#pragma unroll
-        for (int i = 0; i < 6; ++i) Pc[i] = (BC & 1) ? row_bcast_f64_at(E[i], p) : readlane_f64(E[i], p);
-        const double inv = rcp_nr(Pc[p]);
-        const double ep = E[p] * inv;
-#pragma unroll
-        for (int i = 0; i < 6; ++i) E[i] = (i == p) ? ep : E[i] - Pc[i] * ep;
-      }
-      if (ABL & 512) te = tstamp(E[0] + E[1] + E[2] + E[3] + E[4] + E[5]);
-      {  // K~ columns (lanes of G~ columns; (BC & 1) == 0: lane l = column l), others to the sink
-        const bool kw = cc_own >= 6 && cc_own < 19;
-#pragma unroll
-        for (int i = 0; i < 6; ++i) {
-          const double ki = S44 ? E[i] : -E[i];  // S44: the G~ columns were eliminated from -G~
-          if (BF) sh[kw ? MO_KT + 13 * i + (cc_own - 6) : MO_DUMMY + l] = ki;
-          else if (kw) sh[MO_KT + 13 * i + (cc_own - 6)] = ki;
-        }
-      }
-      if (HINV && cc_own >= 19 && cc_own < 25) {
-        double* hk = hinv + ((long)b * (N - 1) + k) * 36;
-#pragma unroll
-        for (int i = 0; i < 6; ++i) hk[6 * i + (cc_own - 19)] = E[i];
-      }
-      wave_sync();
-      if (ABL & 512) tm3 = tstamp(E[0]);
-      if constexpr (X44) {  // Z10 holds -G~ (ric44_g); row blocks 0..2 of V~
+    // W0's v rows for G~; then H = Bu' V_vv Bu + R (under the Qxx chain), G~ = Bu' W0_v + N~,
+    // both stored into MO_H / MO_G for the elimination
+    sh[lo16(M44.w0S)] = W0[1];
+    sh[hi16(M44.w0S)] = W0[2];
+    ric44_h<BOX>(M44, sh);
+    if (!X44) Z00[3] = fma(W0[3], mlq0, Z00[3]);  // row 12's k-step: + W0[12][:] on the lanes lq == 0
+    {
+      // k-step 0 (A~'s q rows 0..3: 1 at (k, k), dt at (k, k + 6)) on the VALU: rows 0..3 of Qxx
+      // gain W0's rows 0..3 (same lanes), rows 6..9 dt times them (the other half of the wave:
+      // one v_permlane32_swap per dword).  One nonzero term per entry, rounded as the MFMA's
+      // k-step rounds it (bit-identical).
+      // Q~'s rank-1 products stay rounded on their own, as the MFMA's C input (otherwise the
+      // compiler contracts them into the adds below)
+      asm volatile("" : "+v"(Z00[0]), "+v"(Z00[1]));
+      Z00[0] = Z00[0] + W0[0];
+      const long long wb = __double_as_longlong(W0[0]);
+      const auto slo = __builtin_amdgcn_permlane32_swap((unsigned)wb, (unsigned)wb, false, false);
+      const auto shi = __builtin_amdgcn_permlane32_swap((unsigned)(wb >> 32), (unsigned)(wb >> 32), false, false);
+      // lanes 32..63 of the first result: W0 from lanes 0..31 (rows 0, 1); lanes 0..31 of the
+      // second: from lanes 32..63 (rows 2, 3)
+      const double up = __longlong_as_double(((long long)shi[0] << 32) | (unsigned)slo[0]);
+      const double dn = __longlong_as_double(((long long)shi[1] << 32) | (unsigned)slo[1]);
+      // (an fma: the MFMA's k-step adds its exact product to C — measured: a separately rounded
+      // product changes 4 091 of 4 096 config-3 solves, the fma none)
+      Z00[1] = fma(up, mdt_hi, Z00[1]);  // rows 6, 7 (lq 2, 3)
+      Z00[2] = fma(dn, mdt_lo, Z00[2]);  // rows 8, 9 (lq 0, 1)
+      if constexpr (X44) {
+        // k-steps 1, 2 as three row blocks each (the 16x16 D registers 0..2)
 #pragma unroll
         for (int rb = 0; rb < 3; ++rb) {
-          V[rb] = mfma44_nb(sh[lo16(vxA[rb])], Z10[0], Z00[rb]);
-          V[rb] = mfma44_nb(sh[hi16(vxA[rb])], Z10[1], V[rb]);
+          Z00[rb] = mfma44(sh[lo16(qxA[rb])], W0[1], Z00[rb]);
+          Z00[rb] = mfma44(sh[hi16(qxA[rb])], W0[2], Z00[rb]);
         }
-      } else if constexpr (S44) {  // Z10 holds -G~ (ric44_g)
-        V = mfma_nb(sh[oK[0]], Z10[0], Z00);
-        V = mfma_nb(sh[oK[1]], Z10[1], V);
       } else {
-        V = mfma(sh[oK[0]], Z10[0], Z00);
-        V = mfma(sh[oK[1]], Z10[1], V);
+#pragma unroll
+        for (int s = 1; s < 3; ++s) Z00 = mfma(bA[s], W0[s], Z00);
       }
-      if (ABL & 512) {
-        const long long tm4 = tstamp(V[0] + V[1] + V[2] + V[3]);
-        if (b == 0 && l == 0) {
-          double* o = sol + 8 * k;
-          o[0] = (double)(ta - tp);    // stash LDS round trip + operand reads (+ MFMA chains)
-          o[2] = (double)(tp - tm0);   // the stash loads of the stage (issued a stage ahead)
-          o[1] = (double)(tb - ta);    // W0 chain
-          o[3] = (double)(tm2 - tm1);  // G~ issue
-          o[4] = (double)(td - tm2);   // H, G~ results -> LDS -> per-lane columns
-          o[5] = (double)(te - td);    // six pivots
-          o[6] = (double)(tm3 - te);   // K~ -> LDS
-          o[7] = (double)(tm4 - tm3);  // V~ update
-        }
+    }
+    ric44_g<BOX>(M44, sh);
+    double* kk = KB + (long)k * KBUF_STRIDE;
+    // Column-per-lane Gauss-Jordan: H, -G~ through LDS, one column of [H | -G~ (| I)] per lane,
+    // the pivot column broadcast by DPP row_newbcast, which stays inside a 16-lane row — so each
+    // of the two rows used carries its own copy of H's six columns: row 0 = H 0..5, G~ 0..9;
+    // row 1 = H 0..5 again, G~ 10..12 and (HINV) the identity columns, which end as H^-1.  The
+    // two copies of H evolve identically.
+    // (stores of lanes with nothing to store go to their own dummy slot: no exec-mask branches)
+    wave_sync();
+    // -G~ in the 16x16x4 B layout (k-steps 0, 1) for V~'s update below
+    d4 nG;
+    nG[0] = sh[lo16(M44.oGB)];
+    nG[1] = sh[hi16(M44.oGB)];
+    double E[6];
+    // column of lane l: 0..5 H, 6..18 G~, 19..24 identity (HINV); -1 unused (rows 2, 3 and
+    // row 1's tail compute a copy of H column 0 and store nothing)
+    const int m16 = l & 15;
+    const int ncol = HINV ? 25 : 19;
+    const int cc_own = !(BC & 1) ? l
+                       : (l < 16) ? m16 : (l < 32 ? (m16 < 6 ? m16 : (m16 < (HINV ? 15 : 9) ? m16 + 10 : -1)) : -1);
+    const int cc = !(BC & 1) ? (l < ncol ? l : ncol - 1) : (cc_own < 0 ? 0 : cc_own);
+    const int eo = (cc < 6) ? MO_H + cc : MO_G + (cc - 6), es = (cc < 6) ? 6 : 13;
+#pragma unroll
+    for (int i = 0; i < 6; ++i) {
+      E[i] = sh[eo + es * (HINV && cc >= 19 ? 0 : i)];
+      if (HINV && cc >= 19) E[i] = (i == cc - 19) ? 1.0 : 0.0;
+    }
+#pragma unroll
+    for (int p = 0; p < 6; ++p) {
+      double Pc[6];
+#pragma unroll
+      for (int i = 0; i < 6; ++i) Pc[i] = (BC & 1) ? row_bcast_f64_at(E[i], p) : readlane_f64(E[i], p);
+      const double inv = rcp_nr(Pc[p]);
+      const double ep = E[p] * inv;
+#pragma unroll
+      for (int i = 0; i < 6; ++i) E[i] = (i == p) ? ep : E[i] - Pc[i] * ep;
+    }
+    {  // K~ columns (lanes of G~ columns; (BC & 1) == 0: lane l = column l), others to the sink;
+       // eliminated from -G~, so they are K~ = -H^-1 G~ as they stand
+      const bool kw = cc_own >= 6 && cc_own < 19;
+#pragma unroll
+      for (int i = 0; i < 6; ++i) {
+        if (BF) sh[kw ? MO_KT + 13 * i + (cc_own - 6) : MO_DUMMY + l] = E[i];
+        else if (kw) sh[MO_KT + 13 * i + (cc_own - 6)] = E[i];
       }
-      if (BOX && kff_only) {
-        // a corrector step of the interior point: same Hessian as the predictor's, so its gain K is
-        // bit for bit the one the predictor stored (each K~ column is eliminated on its own with
-        // H's pivots, and the hom row / column of V~ never enters the first twelve columns); only
-        // the feedforward column changes, and c_v does not
-        if (l < 6) kk[13 * l + 12] = sh[MO_KT + 13 * l + 12];
-      } else {
+    }
+    if (HINV && cc_own >= 19 && cc_own < 25) {
+      double* hk = hinv + ((long)b * (N - 1) + k) * 36;
+#pragma unroll
+      for (int i = 0; i < 6; ++i) hk[6 * i + (cc_own - 19)] = E[i];
+    }
+    wave_sync();
+    // V~ <- Qxx + K~' G~ (the B operand, -G~, negated)
+    if constexpr (X44) {  // row blocks 0..2 of V~
+#pragma unroll
+      for (int rb = 0; rb < 3; ++rb) {
+        V[rb] = mfma44_nb(sh[lo16(vxA[rb])], nG[0], Z00[rb]);
+        V[rb] = mfma44_nb(sh[hi16(vxA[rb])], nG[1], V[rb]);
+      }
+    } else {
+      V = mfma_nb(sh[oK[0]], nG[0], Z00);
+      V = mfma_nb(sh[oK[1]], nG[1], V);
+    }
+    if (BOX && kff_only) {
+      // a corrector step of the interior point: same Hessian as the predictor's, so its gain K is
+      // bit for bit the one the predictor stored (each K~ column is eliminated on its own with
+      // H's pivots, and the hom row / column of V~ never enters the first twelve columns); only
+      // the feedforward column changes, and c_v does not
+      if (l < 6) kk[13 * l + 12] = sh[MO_KT + 13 * l + 12];
+    } else {
       kk[l] = sh[MO_KT + l];
       if (BF) kk[64 + l20] = sh[ko20];  // lanes >= 20 repeat the stores of lanes l % 20 (same values)
       else if (l < 20) kk[64 + l] = (l < 14) ? sh[MO_KT + 64 + l] : sh[MO_CV + (l - 14)];
-      }
     }
   }
 
@@ -1067,12 +885,11 @@ __device__ __forceinline__ void riccati_mfma_body(const int b, const SolveParams
     lds_sync();  // wave 1's last reads of the stage LDS before the rollout reuses it
     if (w != 0) return;
   }
-  if (ABL & 1) return;
-  riccati_rollout<ABL, BC>(b, P, xs, LINb, KB, sol, sh, l);
+  riccati_rollout<BC>(b, P, xs, LINb, KB, sol, sh, l);
 }
 
 // The corrector Newton step of I7M_QP_BOX (k_ipm_fused): the QP of the last
-// riccati_mfma_body<0, true, true> run (same Hessian, dynamics and x_0) with its linear terms
+// riccati_mfma_body<true, true> run (same Hessian, dynamics and x_0) with its linear terms
 // changed by dh (B, T).  The KKT system is linear, so the new minimiser is the old one, y, plus
 // the minimiser of the change: a vector-only Riccati pass with that run's gains K (kbuf) and
 // H^-1 (hinv), zero dynamics offsets and zero initial state:
@@ -1218,11 +1035,11 @@ __global__ void __launch_bounds__(128) k_riccati_mfma_w2(SolveParams P, const do
   if (b >= P.B) return;
   if (active && !active[b]) return;
   __shared__ double sh[MO_TOTAL_W2];
-  riccati_mfma_body<0, false, false, BC, true>(b, P, xu, xs, lin, cost, qpd, kbuf, sol, nullptr, nullptr, sh,
+  riccati_mfma_body<false, false, BC, true>(b, P, xu, xs, lin, cost, qpd, kbuf, sol, nullptr, nullptr, sh,
                                                threadIdx.x & 63);
 }
 
-template <int ABL, bool BOX = false, int BC = 0>
+template <bool BOX = false, int BC = 0>
 __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(4, 4))) k_riccati_mfma(SolveParams P, const double* __restrict__ xu,
                                                      const double* __restrict__ xs, const double* __restrict__ lin,
                                                      const double* __restrict__ cost, const double* __restrict__ qpd,
@@ -1236,7 +1053,7 @@ __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(4, 4)))
   if (b >= P.B) return;
   if (active && !active[b]) return;
   __shared__ double sh[MO_TOTAL];
-  riccati_mfma_body<ABL, BOX, false, BC>(b, P, xu, xs, lin, cost, qpd, kbuf, sol, bsig, bh, sh, threadIdx.x, nullptr,
+  riccati_mfma_body<BOX, false, BC>(b, P, xu, xs, lin, cost, qpd, kbuf, sol, bsig, bh, sh, threadIdx.x, nullptr,
                                          false, vout);
 }
 

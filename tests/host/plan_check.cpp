@@ -146,6 +146,25 @@ static void environment() {
   CHECK(!tuning_from_env(cfg, &t, &err) && err.find("h2h_chunks") != std::string::npos, "h2h_chunks = 65 accepted");
 }
 
+// I7M_ABLATE values of the diagnostic library: the retired Riccati / line-search ones say so, the
+// OSQP and interior-point ones stay known, one that no kernel ever looked at is unknown
+static void ablation_values() {
+  for (int v : {1, 2, 4, 6, 8, 10, 11, 13, 18, 19}) {
+    const AblateStatus s = ablate_status(v);
+    CHECK(s.kind == Ablate::retired && s.msg && std::string(s.msg).find("retired") != std::string::npos,
+          "ablate %d: kind %d message %s", v, (int)s.kind, s.msg ? s.msg : "(none)");
+  }
+  for (int v : {0, 21, 40, 41, 42, 43, 44, 100000 + 100 * 3 + 2, 200000 + 5, 300000 + 4}) {
+    const AblateStatus s = ablate_status(v);
+    CHECK(s.kind == Ablate::known && !s.msg, "ablate %d: kind %d", v, (int)s.kind);
+  }
+  for (int v : {3, 5, 20, 39, 45, -1}) {
+    const AblateStatus s = ablate_status(v);
+    CHECK(s.kind == Ablate::unknown && s.msg && std::string(s.msg).find("retired") == std::string::npos,
+          "ablate %d: kind %d message %s", v, (int)s.kind, s.msg ? s.msg : "(none)");
+  }
+}
+
 // carve: every offset a multiple of 256, no two sub-buffers overlapping, the total covering the last
 static void check_carve(const std::vector<size_t>& bytes, const char* what) {
   std::vector<size_t> off(bytes.size(), ~(size_t)0);
@@ -182,6 +201,7 @@ int main() {
   coverage();
   pinned();
   environment();
+  ablation_values();
   workspace();
   if (g_failed) {
     std::printf("%d check(s) failed\n", g_failed);

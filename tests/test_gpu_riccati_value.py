@@ -17,8 +17,9 @@ reference's 1e-5 / 100) and pins, at N = 32 and N = 64 (the largest horizon the 
       the recursion keeps it to ~1e-13 on these problems, measured; the constant V~[12][12] is not
       formed, I7M_RIC_44X)
 
-A build that forms H from V~_vv instead of V~_vv' (-DI7M_RIC_VV_PLAIN=1) fails the first two
-gates (profiles/r04_vv_plain_variant.log).
+A build that forms H from V~_vv instead of V~_vv' (-DI7M_RIC_VV_PLAIN=1; the switch was folded,
+commit a2cf0e7 is the last tree that has it) failed the first two gates
+(profiles/r04_vv_plain_variant.log).
 """
 import numpy as np
 import pytest

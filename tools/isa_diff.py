@@ -3,7 +3,11 @@ the instruction streams are identical, and the kernel-descriptor fields (registe
 LDS) of both.  Comments are dropped and basic-block labels renumbered per function, so a kernel
 that merely moved in the file compares equal.
 
-    python tools/isa_diff.py OLD.s NEW.s [SUBSTRING_OF_MANGLED_NAME ...]
+    python tools/isa_diff.py OLD.s NEW.s [--rename OLD_SUBSTRING=NEW_SUBSTRING ...] [SUBSTRING_OF_MANGLED_NAME ...]
+
+--rename (repeatable) rewrites the OLD side's mangled names (the kernels' and the symbols their
+instructions refer to) before pairing, for a change that drops or adds a template parameter:
+--rename k_riccati_mfmaILi0E=k_riccati_mfmaI.
 
 Exit status 1 if a kernel is missing on one side or differs.
 """
@@ -41,7 +45,15 @@ def descriptors(text):
 
 
 def main():
-    old, new, pats = open(sys.argv[1]).read(), open(sys.argv[2]).read(), sys.argv[3:]
+    args, renames = sys.argv[1:], []
+    while "--rename" in args:
+        i = args.index("--rename")
+        renames.append(args[i + 1].split("=", 1))
+        del args[i:i + 2]
+    old, new, pats = open(args[0]).read(), open(args[1]).read(), args[2:]
+
+    for a, b in renames:
+        old = old.replace(a, b)
     ko, kn = dict(kernel_bodies(old)), dict(kernel_bodies(new))
     do, dn = descriptors(old), descriptors(new)
     bad = 0
