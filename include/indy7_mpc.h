@@ -40,6 +40,8 @@
  *                              (find_best_idx / resample_f_ext_batch, gato_controller.py:109-129)
  *   i7m_mpc_run_tracking       GATO_Controller.joint_callback: that loop tracking a reference
  *                              trajectory                     gato_controller.py:201-250
+ *   i7m_ctrl_begin / _step / _end   GATO_Controller.__init__ / joint_callback on a state measured
+ *                              outside the device             gato_controller.py:174-185,201-250
  *
  * Layouts (all fp64, C-contiguous, row = problem):
  *   XU    (B, T)  T = 18N-6, [x_0,u_0,x_1,u_1,...,x_{N-1}], x=[q(6),v(6)]  src/osqp_solver.py:22
@@ -81,7 +83,8 @@ extern "C" {
 #define I7M_MAX_N 64
 
 /* ABI revision, returned by i7m_abi_version(); bumped whenever an existing signature, struct
- * layout, field meaning or enum count changes.  7: i7m_mpc_run_tracking (appended; nothing
+ * layout, field meaning or enum count changes.  8: i7m_ctrl_begin / i7m_ctrl_step / i7m_ctrl_end
+ * (appended; nothing existing changed).  7: i7m_mpc_run_tracking (appended; nothing
  * existing changed) (0.7 builds).  6: i7m_get_admm_status has the value 2 ("solved
  * inaccurate") and, after admm_max_iter, runs OSQP's closing tests (0.6 builds).  5: i7m_get_admm_status and i7m_get_admm_dual
  * (appended); i7m_get_admm_stats' iteration record is reset to -1 at the start of every solve
@@ -93,7 +96,7 @@ extern "C" {
  * 2: i7m_aba / i7m_rk4 take a wrench `frame` before their outputs and i7m_set_external_wrench a
  * trailing `frame` (0.2 builds); 1 had neither.  A caller built against another revision must not
  * call through this library: compare first. */
-#define I7M_ABI_VERSION 7
+#define I7M_ABI_VERSION 8
 
 #define I7M_OK 0
 #define I7M_EINVAL -1   /* bad argument (size, null pointer, unsupported N) */
@@ -405,6 +408,75 @@ int i7m_mpc_run_tracking(i7m_handle* h, int32_t G, int32_t H, const double* xsta
                          const double* fhyp, const double* f_actual, const double* noise, const i7m_sampled_opts* opts,
                          double* err_out, int32_t* best_out, double* q_out, double* ee_out, double* fbest_out,
                          double* xcur_out, double* xu_best_out, double* fhyp_out);
+
+/* A controller session: GATO_Controller itself (gato_controller.py:144-250), one control step per
+ * call on a state MEASURED by the caller (a robot, a simulator), where i7m_mpc_run_tracking owns
+ * the plant.  G controllers of H hypotheses, group g owning rows [g H, (g + 1) H) as there; the
+ * session lives on a handle in I7M_QP_DIRECT or I7M_QP_ADMM mode, one at a time.
+ *
+ * i7m_ctrl_begin (:174-185) copies ref (L, ref_stride) and ref_phase (G, or NULL = 0) into device
+ * memory of the handle, sets the rows' wrenches to fhyp (G H, 6) in opts->frame, starts the solver
+ * state afresh, sets every row of group g to XU = [x0[g], 0...], xs = x0[g] and its goals to the
+ * window at offset 0 (goals[k] = ref[min(ph_g + k, L - 1)][0:3]), solves once, sets XU_best[g] =
+ * row g H and writes XU_best[g][12:18] to u_out (G, 6; may be NULL).  opts NULL = the defaults; its
+ * sim_dt and n_actual are ignored.  x0 has two forms:
+ *   x0 (G, 12)  the session remembers x_last[g] = x0[g], u_last[g] = that u_out, which the caller
+ *               applies to its plant: i7m_mpc_run_tracking's start;
+ *   x0 NULL     the controller's constructor: the rows start at the zero state (:181-183) and
+ *               x_last is unset; the first step sets x_last = x_meas, u_last = 0 before it scores
+ *               (:205-206): each hypothesis is then scored by the change of state it predicts
+ *               over `elapsed` under zero torque, not against a control that was applied.
+ *
+ * i7m_ctrl_step (:213-250), x_meas (G, 12) the measured states, `elapsed` the time since the
+ * state x_last was measured (one clock for all groups; finite, > 0, not bounded by dt: it is the
+ * scoring step, not a knot), ref_offset >= 0 the window's offset (the controller's is
+ * int(sum of elapsed / dt)):
+ *   window   every row of g: goals[k] = ref[min(ph_g + ref_offset + k, L - 1)][0:3]
+ *   spread   every row of g: xs = x_meas[g], XU = [x_meas[g], XU_best[g][12:]] (:217-218,249)
+ *   track    ee_out[g] = eepos(x_meas[g] q) (the model's FK; the controller reads it from the
+ *            simulator's message), err_out[g] = |ee - window[0]| (:242)
+ *   score    err_h = |rk4(x_last[g], u_last[g], elapsed, wrench row h) - x_meas[g]|_2 over all 12
+ *            entries: one rk4 step of length elapsed, a world wrench converted once at x_last's q
+ *            as i7m_rk4 does, the hypotheses those before this step's resample (:225); best = the
+ *            lowest index among the minima (a NaN error never wins, all NaN -> 0), where the
+ *            controller's `<=` (:115) takes the highest: tied rows are identical hypotheses
+ *   reset    I7M_QP_ADMM: opts->reset_what on every row (default ALL, :221-223)
+ *   solve    XU_new = sqp(rows)
+ *   select   best_out[g] = best, fbest_out[g] = wrench row best, XU_best[g] = XU_new[g H + best],
+ *            u_out[g] = XU_best[g][12:18]
+ *   resample only with noise (G H, 3), by gato_controller.py:120-129's order with opts->keep_best
+ *            and opts->decay, as i7m_mpc_run_sampled does it
+ *   remember x_last = x_meas, u_last = u_out
+ * The scoring uses no result of the solve and runs before it.  u_out (G, 6) is required; best_out
+ * (G) int32, fbest_out (G, 6), err_out (G), ee_out (G, 3) may be NULL.  A step allocates nothing:
+ * everything it needs, pinned host staging included, is allocated by i7m_ctrl_begin.  It runs as
+ * ONE range on the handle's stream (a session gets no two-stream stagger, whatever G H is), ends
+ * with one device-to-host copy and one synchronisation, and captures no graph.
+ *
+ * i7m_ctrl_end copies out the final XU_best (G, T) and hypotheses (G H, 6) (each may be NULL) and
+ * closes the session; the final hypotheses stay the handle's external wrench in opts->frame, as
+ * after i7m_mpc_run_tracking.  i7m_destroy on a handle with an open session frees it.
+ *
+ * I7M_EINVAL with a message naming the argument, before any device work: an I7M_QP_BOX handle; H
+ * not in {1, 2, 4, ..., 256}; G H outside [0, max_batch]; L < 1; ref_stride other than 3 or 6; a
+ * negative ref_phase entry; a bad frame or reset_what; null ref, fhyp, x_meas or u_out (of a step);
+ * i7m_ctrl_begin while a session is open; i7m_ctrl_step / i7m_ctrl_end without one; a non-finite or
+ * non-positive elapsed; a negative ref_offset; a non-finite entry of x_meas (a host scan of 12 G
+ * doubles: a sensor fault must not poison the carried warm start).  A refused step leaves the
+ * session as it was.
+ * While a session is open the entry points that would overwrite its rows, goals, wrenches or
+ * solver state are refused ("controller session open"): i7m_solve, i7m_solve_device, i7m_qp,
+ * i7m_qp_value, i7m_linearize, i7m_merit, i7m_linesearch, the three i7m_mpc_run*,
+ * i7m_set_external_wrench, i7m_reset, i7m_admm_reset, i7m_set_stream.  The getters, the timing
+ * calls, i7m_synchronize and the query hooks (i7m_eepos, i7m_aba, i7m_aba_derivatives, i7m_rk4:
+ * they use scratch the session does not rely on between steps) stay available. */
+int i7m_ctrl_begin(i7m_handle* h, int32_t G, int32_t H, const double* x0 /* (G,12) or NULL */, const double* ref,
+                   int32_t L, int32_t ref_stride, const int32_t* ref_phase /* (G) or NULL */,
+                   const double* fhyp /* (G H,6) */, const i7m_sampled_opts* opts, double* u_out /* (G,6) or NULL */);
+int i7m_ctrl_step(i7m_handle* h, const double* x_meas /* (G,12) */, double elapsed, int32_t ref_offset,
+                  const double* noise /* (G H,3) or NULL */, double* u_out /* (G,6) */, int32_t* best_out /* (G) */,
+                  double* fbest_out /* (G,6) */, double* err_out /* (G) */, double* ee_out /* (G,3) */);
+int i7m_ctrl_end(i7m_handle* h, double* xu_best_out /* (G,T) or NULL */, double* fhyp_out /* (G H,6) or NULL */);
 
 /* Per-kernel device timing with HIP events on the launch stream. */
 enum { I7M_K_LIN = 0, I7M_K_RICCATI = 1, I7M_K_LINESEARCH = 2, I7M_K_RICCATI_BOX = 3, I7M_K_IPM = 4, I7M_K_IPM_FUSED = 5,

@@ -20,7 +20,7 @@ import numpy as np
 LIB_DIR = os.path.join(os.path.dirname(os.path.abspath(__file__)), "lib")
 LIB_PATH = os.environ.get("I7M_LIB", os.path.join(LIB_DIR, "libindy7mpc.so"))  # I7M_LIB: A/B builds
 
-ABI_VERSION = 7  # I7M_ABI_VERSION of include/indy7_mpc.h this binding's SIGNATURES follow
+ABI_VERSION = 8  # I7M_ABI_VERSION of include/indy7_mpc.h this binding's SIGNATURES follow
 NJ, NX, NU = 6, 12, 6
 MAX_SQP = 8
 MAX_N = 64
@@ -169,6 +169,10 @@ SIGNATURES = [
     ("i7m_mpc_run_tracking", C.c_int, [_H, C.c_int32, C.c_int32, _DP, _DP, C.c_int32, C.c_int32, _IP32, _IP32, C.c_int32,
                                        _DP, _DP, _DP, C.POINTER(i7m_sampled_opts), _DP, _IP32, _DP, _DP, _DP, _DP, _DP,
                                        _DP]),
+    ("i7m_ctrl_begin", C.c_int, [_H, C.c_int32, C.c_int32, _DP, _DP, C.c_int32, C.c_int32, _IP32, _DP,
+                                 C.POINTER(i7m_sampled_opts), _DP]),
+    ("i7m_ctrl_step", C.c_int, [_H, _DP, C.c_double, C.c_int32, _DP, _DP, _IP32, _DP, _DP, _DP]),
+    ("i7m_ctrl_end", C.c_int, [_H, _DP, _DP]),
     ("i7m_set_timing", C.c_int, [_H, C.c_int]),
     ("i7m_get_kernel_times", C.c_int, [_H, _DP, C.POINTER(C.c_int32), C.c_int32]),
     ("i7m_reset_kernel_times", C.c_int, [_H]),
@@ -536,6 +540,70 @@ class Handle:
                                               out["best"].ctypes.data_as(_IP32), _ptr(out["q"]), _ptr(out["ee"]),
                                               _ptr(out["fbest"]), _ptr(out["xcur"]), _ptr(out["xu_best"]),
                                               _ptr(out["fhyp"])))
+        return out
+
+    # ---- the controller session (i7m_ctrl_begin / _step / _end) ----------------------------
+    def ctrl_begin(self, ref, fhyp, x0=None, groups=None, ref_phase=None, frame="world", reset_what=ADMM_RESET_ALL,
+                   keep_best=False, decay=1.0):
+        """Open a controller session (i7m_ctrl_begin): G controllers of H hypotheses tracking ref
+        (L, 3) or (L, 6) from measured states.  x0 (G, 12): the start states, remembered as x_last
+        with the returned control as u_last; x0 None: the controller's constructor (rows at the
+        zero state, the first step scores from x_last = x_meas, u_last = 0), G = `groups` (default
+        1).  fhyp (G * H, 6), ref_phase (G,) or None.  Returns u (G, 6), the initial solve's control."""
+        rf = _f64(ref)
+        if rf.ndim != 2:
+            raise ValueError("ref must be (L, 3) or (L, 6)")
+        L, stride = rf.shape
+        xs = None if x0 is None else _f64(x0).reshape(-1, NX)
+        G = int(groups) if groups is not None else (1 if xs is None else xs.shape[0])
+        if xs is not None and xs.shape[0] != G:
+            raise ValueError(f"x0 must be ({G}, 12)")
+        fh = _f64(fhyp).reshape(-1, 6)
+        if G < 1 or fh.shape[0] % G:
+            raise ValueError(f"fhyp has {fh.shape[0]} rows, not a multiple of the {G} groups")
+        Hn = fh.shape[0] // G
+        rp = None
+        if ref_phase is not None:
+            rp = np.ascontiguousarray(ref_phase, dtype=np.int32).reshape(-1)
+            if rp.shape[0] != G:
+                raise ValueError(f"ref_phase must be ({G},)")
+        o = i7m_sampled_opts()
+        _check(self._lib.i7m_sampled_opts_default(C.byref(o)))
+        o.decay, o.frame, o.reset_what, o.keep_best = float(decay), _FRAMES[frame], int(reset_what), int(bool(keep_best))
+        u = np.empty((G, NU))
+        _check(self._lib.i7m_ctrl_begin(self._h, G, Hn, _ptr(xs) if xs is not None else None, _ptr(rf), L, stride,
+                                        rp.ctypes.data_as(_IP32) if rp is not None else None, _ptr(fh), C.byref(o),
+                                        _ptr(u)))
+        self._ctrl = (G, Hn)
+        return u
+
+    def ctrl_step(self, x_meas, elapsed, ref_offset, noise=None):
+        """One controller step on the measured states x_meas (G, 12) (i7m_ctrl_step): elapsed the
+        time since the previous measurement, ref_offset the window's offset, noise (G * H, 3) or
+        None (no resampling this step).  Returns a dict: u (G, 6) the controls to apply, best (G,)
+        int32, fbest (G, 6), err (G,) the tracking error, ee (G, 3)."""
+        G, Hn = getattr(self, "_ctrl", None) or (np.size(x_meas) // NX, 0)
+        xm = _f64(x_meas).reshape(G, NX)
+        nz = None
+        if noise is not None:
+            nz = _f64(noise)
+            if nz.size != G * Hn * 3:
+                raise ValueError(f"noise must be ({G * Hn}, 3)")
+        out = dict(u=np.empty((G, NU)), best=np.empty(G, dtype=np.int32), fbest=np.empty((G, 6)), err=np.empty(G),
+                   ee=np.empty((G, 3)))
+        _check(self._lib.i7m_ctrl_step(self._h, _ptr(xm), float(elapsed), int(ref_offset),
+                                       _ptr(nz) if nz is not None else None, _ptr(out["u"]),
+                                       out["best"].ctypes.data_as(_IP32), _ptr(out["fbest"]), _ptr(out["err"]),
+                                       _ptr(out["ee"])))
+        return out
+
+    def ctrl_end(self):
+        """Close the session (i7m_ctrl_end).  Returns a dict: xu_best (G, T) the final XU_best, fhyp
+        (G * H, 6) the final hypotheses (left set on the handle)."""
+        G, Hn = getattr(self, "_ctrl", None) or (0, 0)
+        out = dict(xu_best=np.empty((G, self.T)), fhyp=np.empty((G * Hn, 6)))
+        _check(self._lib.i7m_ctrl_end(self._h, _ptr(out["xu_best"]), _ptr(out["fhyp"])))
+        self._ctrl = None
         return out
 
     # ---- timing --------------------------------------------------------------------------

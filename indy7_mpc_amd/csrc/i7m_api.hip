@@ -25,6 +25,7 @@
 #include "i7m_admm_iter.h"
 #include "i7m_mpc.h"
 #include "i7m_mpc_sampled.h"
+#include "i7m_ctrl.h"
 #include "i7m_plan.h"
 
 // Source hash of the tree this library was built from (__graft_entry__.build passes it), so
@@ -83,6 +84,20 @@ struct Timing {
 
 }  // namespace
 
+// A controller session (i7m_ctrl_begin .. i7m_ctrl_end): one device allocation and one pinned host
+// allocation, carved by i7m_plan.h's ctrl_ws_bytes / ctrl_host_bytes, and what the steps carry.
+struct CtrlSession {
+  bool open = false;
+  int G = 0, H = 0;
+  bool have_last = false;  // x_last / u_last are set (i7m_ctrl_begin with x0, or a step has run)
+  i7m_sampled_opts o{};
+  char *dev = nullptr, *host = nullptr;
+  size_t doff[CTRL_WS_COUNT] = {}, hoff[CTRL_HS_COUNT] = {};
+  CtrlArgs a{};  // the launches' arguments, all but the step's own (elapsed, off, noise, have_last, initial)
+  template <class P> P* d(int i) const { return reinterpret_cast<P*>(dev + doff[i]); }
+  template <class P> P* p(int i) const { return reinterpret_cast<P*>(host + hoff[i]); }
+};
+
 struct i7m_handle {
   i7m_config cfg;
   long N = 0, T = 0;  // the horizon and the length of an XU row, 18 N - 6
@@ -120,6 +135,7 @@ struct i7m_handle {
   };
   std::vector<GraphEntry> graphs;
   unsigned long long graph_clock = 0;
+  CtrlSession ctrl;  // the controller session, if one is open
   Tuning tune;  // the launch knobs (i7m_plan.h: tuning_from_env at i7m_create)
   double* d_lsbase = nullptr;  // (max_batch) base merits handed to the second launch
   int* d_lspend = nullptr;     // (max_batch) pending flags
@@ -184,8 +200,16 @@ SolveParams params_of(const i7m_handle* h, int B, int goal_stride) {
   return P;
 }
 
+// What every entry point that would overwrite the rows, goals, wrenches or solver state a
+// controller session carries answers while one is open.
+int session_open() {
+  return fail(I7M_EINVAL, "controller session open: this entry point would overwrite what the session carries "
+                          "(i7m_ctrl_end first)");
+}
+
 int check_batch(const i7m_handle* h, int B, int goal_stride) {
   if (!h) return fail(I7M_EINVAL, "null handle");
+  if (h->ctrl.open) return session_open();
   if (B < 0 || B > h->cfg.max_batch)
     return fail(I7M_EINVAL, "batch " + std::to_string(B) + " outside [0, max_batch=" +
                                 std::to_string(h->cfg.max_batch) + "]");
@@ -239,6 +263,14 @@ bool dev_alloc(i7m_handle* h, P** p, size_t bytes) {
   h->owned.push_back(q);
   *p = static_cast<P*>(q);
   return true;
+}
+
+// The controller session's two allocations back (i7m_ctrl_end, i7m_destroy); nothing queued may
+// still use them.
+void ctrl_release(i7m_handle* h) {
+  if (h->ctrl.dev) (void)hipFree(h->ctrl.dev);
+  if (h->ctrl.host) (void)hipHostFree(h->ctrl.host);
+  h->ctrl = CtrlSession{};
 }
 
 // Per-problem work buffers of a contiguous range of problems [b0, b0 + B): every kernel indexes
@@ -1219,6 +1251,7 @@ void i7m_destroy(i7m_handle* h) {
   (void)hipSetDevice(h->dev);
   if (h->stream) (void)hipStreamSynchronize(h->stream);
   for (void* p : h->owned) (void)hipFree(p);
+  ctrl_release(h);
   for (auto& t : h->ev) {
     (void)hipEventDestroy(t.a);
     (void)hipEventDestroy(t.b);
@@ -1246,12 +1279,14 @@ void i7m_destroy(i7m_handle* h) {
 
 int i7m_set_stream(i7m_handle* h, void* stream) {
   if (!h) return fail(I7M_EINVAL, "null handle");
+  if (h->ctrl.open) return session_open();
   h->stream = stream ? (hipStream_t)stream : h->own;
   return I7M_OK;
 }
 
 int i7m_set_external_wrench(i7m_handle* h, int32_t B, const double* fext, int32_t frame) {
   if (!h) return fail(I7M_EINVAL, "null handle");
+  if (h->ctrl.open) return session_open();
   if (!fext) {
     h->has_fext = false;
     drop_graphs(h);  // captured graphs hold the wrench kernel choice
@@ -1273,6 +1308,7 @@ int i7m_set_external_wrench(i7m_handle* h, int32_t B, const double* fext, int32_
 
 int i7m_reset(i7m_handle* h) {
   if (!h) return fail(I7M_EINVAL, "null handle");
+  if (h->ctrl.open) return session_open();
   HIPCHK(hipSetDevice(h->dev));
   HIPCHK(hipStreamSynchronize(h->stream));
   drop_graphs(h);
@@ -1284,6 +1320,7 @@ int i7m_reset(i7m_handle* h) {
 }
 
 int i7m_admm_reset(i7m_handle* h, int32_t B, int32_t what) {
+  if (h && h->ctrl.open) return session_open();
   AdmmArgs a{};
   int rc = admm_rows(h, B, &a);
   if (rc) return rc;
@@ -1603,6 +1640,7 @@ int sampled_loop(i7m_handle* h, const std::string& who, bool track, int32_t G, i
                  const i7m_sampled_opts* opts, double* dist_out, int32_t* best_out, double* q_out, double* ee_out,
                  double* fbest_out, double* xcur_out, double* xu_best_out, double* fhyp_out) {
   if (!h) return fail(I7M_EINVAL, "null handle");
+  if (h->ctrl.open) return session_open();
   i7m_sampled_opts o;
   (void)i7m_sampled_opts_default(&o);
   if (opts) o = *opts;
@@ -1785,6 +1823,215 @@ int i7m_mpc_run_tracking(i7m_handle* h, int32_t G, int32_t H, const double* xsta
   gs.ref_offset = ref_offset;
   return sampled_loop(h, "mpc_run_tracking", true, G, H, xstart, gs, num_steps, fhyp, f_actual, noise, opts, err_out,
                       best_out, q_out, ee_out, fbest_out, xcur_out, xu_best_out, fhyp_out);
+}
+
+}  // extern "C"
+
+namespace {
+
+// The message of a refusal by ctrl_begin_args_ok / ctrl_step_args_ok (i7m_plan.h).
+std::string ctrl_refusal(const i7m_handle* h, const std::string& who, const std::string& which, long at) {
+  const std::string v = std::to_string(at);
+  if (which == "qp_mode") return who + ": I7M_QP_BOX is not supported (I7M_QP_DIRECT or I7M_QP_ADMM)";
+  if (which == "H") return who + ": H = " + v + " is not one of 1, 2, 4, ..., 256";
+  if (which == "G") return who + ": G x H = " + v + " rows outside [0, max_batch=" + std::to_string(h->cfg.max_batch) + "]";
+  if (which == "L") return who + ": L = " + v + ", the reference needs >= 1 point";
+  if (which == "ref_stride") return who + ": ref_stride = " + v + " is not 3 or 6";
+  if (which == "frame") return who + ": frame must be I7M_WRENCH_LOCAL or I7M_WRENCH_WORLD";
+  if (which == "reset_what") return who + ": reset_what has unknown I7M_ADMM_RESET_* bits";
+  if (which == "ref_phase") return who + ": ref_phase[" + v + "] is negative";
+  if (which == "elapsed") return who + ": elapsed must be finite and > 0";
+  if (which == "ref_offset") return who + ": ref_offset = " + v + " is negative";
+  if (which == "x_meas" && at >= 0) return who + ": x_meas[" + v + "] is not finite";
+  return who + ": null " + which;
+}
+
+// The session's solve: opts->reset_what on every row (I7M_QP_ADMM), then the rows' SQP from XU into
+// d_out, one range on the handle's stream.
+int ctrl_solve(i7m_handle* h, int what) {
+  const CtrlSession& c = h->ctrl;
+  const int B = c.G * c.H;
+  int rc;
+  if (h->cfg.qp_mode == I7M_QP_ADMM && what &&
+      (rc = admm_reset_rows(h, 0, B, what, h->stream, c.d<double>(CWS_RHO0), hipMemcpyDeviceToDevice)))
+    return rc;
+  return run_sqp(h, B, h->d_xu, h->d_out, h->d_xs, h->d_goal, 3, nullptr);
+}
+
+void ctrl_launch_select(i7m_handle* h, const CtrlArgs& a) {
+  hipLaunchKernelGGL(k_ctrl_select, dim3(h->ctrl.G), dim3((h->ctrl.H + 63) / 64 * 64), 0, h->stream, a);
+}
+
+}  // namespace
+
+extern "C" {
+
+int i7m_ctrl_begin(i7m_handle* h, int32_t G, int32_t H, const double* x0, const double* ref, int32_t L,
+                   int32_t ref_stride, const int32_t* ref_phase, const double* fhyp, const i7m_sampled_opts* opts,
+                   double* u_out) {
+  const std::string who = "ctrl_begin";
+  if (!h) return fail(I7M_EINVAL, "null handle");
+  if (h->ctrl.open) return fail(I7M_EINVAL, who + ": a controller session is already open on this handle");
+  i7m_sampled_opts o;
+  (void)i7m_sampled_opts_default(&o);
+  if (opts) o = *opts;
+  const char* which = "";
+  long at = 0;
+  if (!ctrl_begin_args_ok(h->cfg.qp_mode, h->cfg.max_batch, G, H, L, ref_stride, ref, ref_phase, fhyp, o.frame,
+                          o.reset_what, &which, &at))
+    return fail(I7M_EINVAL, ctrl_refusal(h, who, which, at));
+  HIPCHK(hipSetDevice(h->dev));
+  HIPCHK(hipStreamSynchronize(h->stream));
+  const int N = (int)h->N, B = G * H;
+  const size_t T = h->T;
+  CtrlSession& c = h->ctrl;
+  size_t db[CTRL_WS_COUNT], hb[CTRL_HS_COUNT];
+  ctrl_ws_bytes(G, H, N, L, ref_stride, ref_phase != nullptr, db);
+  ctrl_host_bytes(G, H, hb);
+  const size_t dtotal = carve(db, CTRL_WS_COUNT, c.doff), htotal = carve(hb, CTRL_HS_COUNT, c.hoff);
+  if (hipMalloc((void**)&c.dev, dtotal ? dtotal : WS_ALIGN) != hipSuccess) {
+    ctrl_release(h);
+    return fail(I7M_ENOMEM, who + ": device allocation failed");
+  }
+  if (hipHostMalloc((void**)&c.host, htotal ? htotal : WS_ALIGN, hipHostMallocDefault) != hipSuccess) {
+    ctrl_release(h);
+    return fail(I7M_ENOMEM, who + ": pinned host allocation failed");
+  }
+  c.G = G;
+  c.H = H;
+  c.o = o;
+  c.have_last = x0 != nullptr;
+  CtrlArgs& a = c.a;
+  a.N = N;
+  a.H = H;
+  a.frame_world = o.frame == I7M_WRENCH_WORLD;
+  a.keep_best = o.keep_best != 0;
+  a.decay = o.decay;
+  a.xs = h->d_xs;
+  a.XU = h->d_xu;
+  a.xu_new = h->d_out;
+  a.goals = h->d_goal;
+  a.fext = h->d_fext;
+  a.x_meas = c.d<double>(CWS_XMEAS);
+  a.x_last = c.d<double>(CWS_XLAST);
+  a.u_last = c.d<double>(CWS_ULAST);
+  a.xub = c.d<double>(CWS_XUB);
+  a.best = c.d<int>(CWS_BEST);
+  a.rec = c.d<double>(CWS_REC);
+  a.ref = c.d<double>(CWS_REF);
+  a.ref_phase = ref_phase ? c.d<int>(CWS_PHASE) : nullptr;
+  a.L = L;
+  a.ref_stride = ref_stride;
+  // gato_controller.py:174-185: the window at offset 0, XU = [x0, 0...] (x0 NULL: the zero state),
+  // the hypotheses set on the solver, its state afresh, one solve, XU_best = row 0 of every group
+  const LoopStart start(h, B, G, H, ref, L, ref_stride, ref_phase);
+  std::vector<double> xrows((size_t)B * 12, 0.0), rho0((size_t)B, h->cfg.admm_rho);
+  for (size_t b = 0; x0 && b < (size_t)B; ++b)
+    for (int r = 0; r < 12; ++r) xrows[b * 12 + r] = x0[(b / H) * 12 + r];
+  int rc = I7M_OK;
+  const auto stage = [&]() -> int {
+    int r;
+    if ((r = copy_in(h, c.d<double>(CWS_REF), ref, (size_t)L * ref_stride))) return r;
+    if (ref_phase) HIPCHK(hipMemcpyAsync(c.d<int>(CWS_PHASE), ref_phase, 4 * (size_t)G, hipMemcpyHostToDevice, h->stream));
+    if ((r = copy_in(h, c.d<double>(CWS_RHO0), rho0.data(), rho0.size()))) return r;
+    if (x0 && (r = copy_in(h, c.d<double>(CWS_XMEAS), x0, (size_t)G * 12))) return r;
+    if ((r = copy_in(h, h->d_goal, start.goals.data(), start.goals.size()))) return r;
+    if ((r = copy_in(h, h->d_xs, xrows.data(), xrows.size()))) return r;
+    HIPCHK(hipMemsetAsync(h->d_xu, 0, 8 * (size_t)B * T, h->stream));
+    if (B > 0)
+      HIPCHK(hipMemcpy2DAsync(h->d_xu, T * 8, xrows.data(), 12 * 8, 12 * 8, (size_t)B, hipMemcpyHostToDevice, h->stream));
+    HIPCHK(hipMemsetAsync(h->d_fext, 0, (size_t)h->cfg.max_batch * 6 * 8, h->stream));
+    if ((r = copy_in(h, h->d_fext, fhyp, (size_t)B * 6))) return r;
+    HIPCHK(hipStreamSynchronize(h->stream));
+    h->has_fext = true;
+    h->fext_frame = o.frame;
+    drop_graphs(h);  // captured graphs hold the old wrench kernel choice
+    if (G == 0) return I7M_OK;
+    if ((r = ctrl_solve(h, I7M_ADMM_RESET_ALL))) return r;
+    CtrlArgs s = a;
+    s.initial = 1;
+    s.noise = nullptr;
+    s.x_meas = x0 ? a.x_meas : nullptr;
+    ctrl_launch_select(h, s);
+    HIPCHK(hipGetLastError());
+    if ((r = copy_out(h, c.p<double>(CHS_REC), a.rec, (size_t)G * CTRL_REC))) return r;
+    HIPCHK(hipStreamSynchronize(h->stream));
+    return I7M_OK;
+  };
+  if ((rc = stage())) {
+    const std::string msg = g_err;
+    (void)hipStreamSynchronize(h->stream);
+    ctrl_release(h);
+    g_err = msg;
+    return rc;
+  }
+  for (int g = 0; u_out && g < G; ++g)
+    for (int k = 0; k < 6; ++k) u_out[6 * g + k] = c.p<double>(CHS_REC)[(size_t)g * CTRL_REC + CREC_U + k];
+  c.open = true;
+  return I7M_OK;
+}
+
+int i7m_ctrl_step(i7m_handle* h, const double* x_meas, double elapsed, int32_t ref_offset, const double* noise,
+                  double* u_out, int32_t* best_out, double* fbest_out, double* err_out, double* ee_out) {
+  const std::string who = "ctrl_step";
+  if (!h) return fail(I7M_EINVAL, "null handle");
+  CtrlSession& c = h->ctrl;
+  if (!c.open) return fail(I7M_EINVAL, who + ": no controller session is open on this handle (i7m_ctrl_begin)");
+  const char* which = "";
+  long at = 0;
+  if (!ctrl_step_args_ok(x_meas, c.G, elapsed, ref_offset, u_out, &which, &at))
+    return fail(I7M_EINVAL, ctrl_refusal(h, who, which, at));
+  if (c.G == 0) return I7M_OK;
+  HIPCHK(hipSetDevice(h->dev));
+  const size_t G = c.G, B = G * c.H;
+  // the whole step as one range on the handle's stream: copy-in, measure, reset, solve, select, one
+  // copy-out, one synchronisation
+  double *px = c.p<double>(CHS_XMEAS), *pn = c.p<double>(CHS_NOISE), *pr = c.p<double>(CHS_REC);
+  std::memcpy(px, x_meas, 8 * 12 * G);
+  if (noise) std::memcpy(pn, noise, 8 * 3 * B);
+  int rc;
+  if ((rc = copy_in(h, c.d<double>(CWS_XMEAS), px, 12 * G))) return rc;
+  if (noise && (rc = copy_in(h, c.d<double>(CWS_NOISE), pn, 3 * B))) return rc;
+  CtrlArgs a = c.a;
+  a.elapsed = elapsed;
+  a.off = ref_offset;
+  a.have_last = c.have_last;
+  a.initial = 0;
+  a.noise = noise ? c.d<double>(CWS_NOISE) : nullptr;
+  hipLaunchKernelGGL(k_ctrl_measure, dim3(c.G), dim3((c.H + 63) / 64 * 64), 0, h->stream, h->d_model, a);
+  HIPCHK(hipGetLastError());
+  if ((rc = ctrl_solve(h, c.o.reset_what))) return rc;
+  ctrl_launch_select(h, a);
+  HIPCHK(hipGetLastError());
+  if ((rc = copy_out(h, pr, a.rec, G * CTRL_REC))) return rc;
+  HIPCHK(hipStreamSynchronize(h->stream));
+  c.have_last = true;
+  for (size_t g = 0; g < G; ++g) {
+    const double* r = pr + g * CTRL_REC;
+    for (int k = 0; k < 6; ++k) u_out[6 * g + k] = r[CREC_U + k];
+    if (best_out) best_out[g] = (int32_t)r[CREC_BEST];
+    for (int k = 0; fbest_out && k < 6; ++k) fbest_out[6 * g + k] = r[CREC_FBEST + k];
+    if (err_out) err_out[g] = r[CREC_ERR];
+    for (int k = 0; ee_out && k < 3; ++k) ee_out[3 * g + k] = r[CREC_EE + k];
+  }
+  return I7M_OK;
+}
+
+int i7m_ctrl_end(i7m_handle* h, double* xu_best_out, double* fhyp_out) {
+  if (!h) return fail(I7M_EINVAL, "null handle");
+  CtrlSession& c = h->ctrl;
+  if (!c.open) return fail(I7M_EINVAL, "ctrl_end: no controller session is open on this handle (i7m_ctrl_begin)");
+  HIPCHK(hipSetDevice(h->dev));
+  const size_t G = c.G, B = G * c.H;
+  int rc = I7M_OK;
+  if (xu_best_out) rc = copy_out(h, xu_best_out, c.a.xub, G * h->T);
+  if (!rc && fhyp_out) rc = copy_out(h, fhyp_out, h->d_fext, B * 6);
+  const std::string msg = g_err;
+  const hipError_t e = hipStreamSynchronize(h->stream);
+  ctrl_release(h);  // the session closes whatever the copies did
+  if (rc) return fail(rc, msg);
+  if (e != hipSuccess) return fail(I7M_EHIP, std::string("hipStreamSynchronize: ") + hipGetErrorString(e));
+  return I7M_OK;
 }
 
 int i7m_set_timing(i7m_handle* h, int enable) {

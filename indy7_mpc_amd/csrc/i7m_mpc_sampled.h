@@ -99,6 +99,102 @@ __device__ __forceinline__ void wave_argmin(double& e, int& i) {
   }
 }
 
+// ---- the pieces k_sampled_step and the controller step (i7m_ctrl.h) share: one workgroup per group,
+// lane l of nt, every __syncthreads under a workgroup-uniform condition; the row pointers are
+// already offset to the group's first row ------------------------------------------------------------
+
+// select + resample: XU_best[g] = row b of the last solve; with `record`, fb = wrench row b, and with
+// noise the group's wrench rows are rewritten in place in gato_controller.py:120-129's order.  The
+// caller synchronises before anything reads XU_best or the rows.
+__device__ __forceinline__ void select_resample(double* xub, const double* xu_new, double* fext, const double* noise,
+                                                int b, int H, int T, int l, int nt, bool record, bool keep_best,
+                                                double decay, double fb[6]) {
+  const double* src = xu_new + (long)b * T;
+  for (int e = l; e < T; e += nt) xub[e] = src[e];
+  if (!record) return;
+#pragma unroll
+  for (int k = 0; k < 6; ++k) fb[k] = fext[b * 6 + k];
+  if (noise) {
+    __syncthreads();  // every lane has read row `best` before its lane rewrites it
+    if (l < H) {
+      double row[6];
+#pragma unroll
+      for (int k = 0; k < 6; ++k) row[k] = fb[k];
+#pragma unroll
+      for (int k = 0; k < 3; ++k) row[k] += noise[l * 3 + k];
+      if (keep_best && l == b)
+#pragma unroll
+        for (int k = 0; k < 6; ++k) row[k] = fb[k];
+#pragma unroll
+      for (int k = 3; k < 6; ++k) row[k] = 0.0;
+      if (l == 0)
+#pragma unroll
+        for (int k = 0; k < 3; ++k) row[k] = 0.0;
+#pragma unroll
+      for (int k = 0; k < 6; ++k) fext[l * 6 + k] = row[k] * decay;
+    }
+  }
+}
+
+// |[qo, vo] - xn|_2 over all 12 entries: a hypothesis's scoring error
+__device__ __forceinline__ double state_err(const double qo[6], const double vo[6], const double xn[12]) {
+  double ss = 0.0;
+#pragma unroll
+  for (int k = 0; k < 6; ++k) {
+    const double dq = qo[k] - xn[k];
+    ss += dq * dq;
+  }
+#pragma unroll
+  for (int k = 0; k < 6; ++k) {
+    const double dv = vo[k] - xn[6 + k];
+    ss += dv * dv;
+  }
+  return sqrt(ss);
+}
+
+// The group's argmin in two halves around the caller's __syncthreads: lane l's (err, l) reduced over
+// its wave and parked (a NaN error and a lane past H never win), then lane 0 merges the waves into
+// the winner: the lowest index among the minima, 0 if every error was NaN.
+__device__ __forceinline__ void group_argmin_park(double& err, int& idx, int l, int H, double* s_err, int* s_idx) {
+  const double inf = __builtin_inf();
+  if (!(err < inf) || l >= H) err = inf;  // a NaN error never wins
+  idx = l;
+  wave_argmin(err, idx);
+  if ((l & 63) == 0) {
+    s_err[l >> 6] = err;
+    s_idx[l >> 6] = idx;
+  }
+}
+__device__ __forceinline__ int group_argmin_merge(double err, int idx, int nt, int H, const double* s_err,
+                                                  const int* s_idx) {
+  for (int w = 1; w < (nt >> 6); ++w)
+    if (s_err[w] < err) {  // a later wave's indices are higher: it wins only if strictly lower
+      err = s_err[w];
+      idx = s_idx[w];
+    }
+  return idx < H ? idx : 0;
+}
+
+// spread: every row of the group gets xs = s_x and XU = [s_x, XU_best[12:]]; lane-contiguous
+// columns, one load and H stores per column
+__device__ __forceinline__ void spread_rows(double* XU, double* xs, const double* xub, const double* s_x, int H, int T,
+                                            int l, int nt) {
+  for (int e = l; e < T; e += nt) {
+    const double v = e < 12 ? s_x[e] : xub[e];
+    for (int hh = 0; hh < H; ++hh) XU[(long)hh * T + e] = v;
+  }
+  for (int e = l; e < 12 * H; e += nt) xs[e] = s_x[e % 12];
+}
+
+// the window: one load per column (knot e / 3, coordinate e % 3) and H stores
+__device__ __forceinline__ void window_rows(double* goals, const double* ref, long ph, long off, int L, int ref_stride,
+                                            int N, int H, int l, int nt) {
+  for (int e = l; e < 3 * N; e += nt) {
+    const double v = ref[track_index(ph, off, e / 3, L) * ref_stride + e % 3];
+    for (int hh = 0; hh < H; ++hh) goals[(long)hh * 3 * N + e] = v;
+  }
+}
+
 // One workgroup per group, one lane per hypothesis (H lanes rounded up to whole waves, <= 4 waves).
 __global__ void __launch_bounds__(256) k_sampled_step(const DevModel* __restrict__ Mg, const SampledArgs A) {
   const int g = blockIdx.x, l = threadIdx.x, nt = blockDim.x;
@@ -124,36 +220,14 @@ __global__ void __launch_bounds__(256) k_sampled_step(const DevModel* __restrict
 
   if (A.select) {
     const int b = A.best[g];
-    const double* src = A.xu_new + (r0 + b) * T;
-    for (int e = l; e < T; e += nt) xub[e] = src[e];
-    if (A.select == 1) {
-      double fb[6];
-#pragma unroll
-      for (int k = 0; k < 6; ++k) fb[k] = A.fext[(r0 + b) * 6 + k];
-      if (A.best_out && l == 0) A.best_out[g] = b;
-      if (A.fbest_out && l == 0)
+    double fb[6];
+    select_resample(xub, A.xu_new + r0 * T, A.fext + r0 * 6, A.noise ? A.noise + r0 * 3 : nullptr, b, H, T, l, nt,
+                    A.select == 1, A.keep_best != 0, A.decay, fb);
+    if (A.select == 1 && l == 0) {
+      if (A.best_out) A.best_out[g] = b;
+      if (A.fbest_out)
 #pragma unroll
         for (int k = 0; k < 6; ++k) A.fbest_out[6L * g + k] = fb[k];
-      if (A.noise) {
-        __syncthreads();  // every lane has read row `best` before its lane rewrites it
-        if (l < H) {
-          double row[6];
-#pragma unroll
-          for (int k = 0; k < 6; ++k) row[k] = fb[k];
-#pragma unroll
-          for (int k = 0; k < 3; ++k) row[k] += A.noise[(r0 + l) * 3 + k];
-          if (A.keep_best && l == b)
-#pragma unroll
-            for (int k = 0; k < 6; ++k) row[k] = fb[k];
-#pragma unroll
-          for (int k = 3; k < 6; ++k) row[k] = 0.0;
-          if (l == 0)
-#pragma unroll
-            for (int k = 0; k < 3; ++k) row[k] = 0.0;
-#pragma unroll
-          for (int k = 0; k < 6; ++k) A.fext[(r0 + l) * 6 + k] = row[k] * A.decay;
-        }
-      }
     }
     __syncthreads();  // XU_best and the resampled rows are the plant's and the score's inputs
   }
@@ -179,40 +253,18 @@ __global__ void __launch_bounds__(256) k_sampled_step(const DevModel* __restrict
         xn[6 + k] = vo[k];
       }
     } else {
-      double ss = 0.0;
-#pragma unroll
-      for (int k = 0; k < 6; ++k) {
-        const double dq = qo[k] - xn[k];
-        ss += dq * dq;
-      }
-#pragma unroll
-      for (int k = 0; k < 6; ++k) {
-        const double dv = vo[k] - xn[6 + k];
-        ss += dv * dv;
-      }
-      err = sqrt(ss);
+      err = state_err(qo, vo, xn);
     }
   }
-  const double inf = __builtin_inf();
-  if (!(err < inf) || l >= H) err = inf;  // a NaN error never wins
-  int idx = l;
-  wave_argmin(err, idx);
-  if ((l & 63) == 0) {
-    s_err[l >> 6] = err;
-    s_idx[l >> 6] = idx;
-  }
+  int idx;
+  group_argmin_park(err, idx, l, H, s_err, s_idx);
   if (l == 0) {
 #pragma unroll
     for (int k = 0; k < 12; ++k) s_x[k] = xn[k];
   }
   __syncthreads();
   if (l == 0) {
-    for (int w = 1; w < (nt >> 6); ++w)
-      if (s_err[w] < err) {  // a later wave's indices are higher: it wins only if strictly lower
-        err = s_err[w];
-        idx = s_idx[w];
-      }
-    A.best[g] = idx < H ? idx : 0;
+    A.best[g] = group_argmin_merge(err, idx, nt, H, s_err, s_idx);
     // the goal of the new state (src/gato_mpc_batch_sample.py:203-217), or the window's first point
     double c[6], s[6], p[3];
     sincos6(xn, c, s);
@@ -237,21 +289,11 @@ __global__ void __launch_bounds__(256) k_sampled_step(const DevModel* __restrict
   }
   if (l < 12) A.xcur[12L * g + l] = s_x[l];
   if (A.q_out && l < 6) A.q_out[6L * g + l] = s_x[l];
-  // spread: lane-contiguous columns, one load and H stores per column
-  for (int e = l; e < T; e += nt) {
-    const double v = e < 12 ? s_x[e] : xub[e];
-    for (int hh = 0; hh < H; ++hh) A.XU[(r0 + hh) * T + e] = v;
-  }
-  for (int e = l; e < 12 * H; e += nt) A.xs[r0 * 12 + e] = s_x[e % 12];
+  spread_rows(A.XU + r0 * T, A.xs + r0 * 12, xub, s_x, H, T, l, nt);
   __syncthreads();
   const int sw = s_switch;
   if (track) {
-    // the window: one load per column (knot e / 3, coordinate e % 3) and H stores
-    double* gl = A.goals + r0 * 3 * N;
-    for (int e = l; e < 3 * N; e += nt) {
-      const double v = A.ref[track_index(ph, A.off, e / 3, A.L) * A.ref_stride + e % 3];
-      for (int hh = 0; hh < H; ++hh) gl[(long)hh * 3 * N + e] = v;
-    }
+    window_rows(A.goals + r0 * 3 * N, A.ref, ph, A.off, A.L, A.ref_stride, N, H, l, nt);
   } else if (sw >= 0) {
     double* gl = A.goals + r0 * 3 * N;
     for (int e = l; e < 3 * N * H; e += nt) gl[e] = A.endpoints[3 * sw + e % 3];

@@ -1,10 +1,12 @@
 // i7m_plan.h — the launch plan of libindy7mpc.so as pure host code: which kernel variant a launch
 // of a given size runs, whether a batch staggers, where its ranges and chunks begin, and how a
-// closed loop's per-call workspace is carved.  No HIP here (tests/host/plan_check.cpp compiles it
+// closed loop's per-call workspace and a controller session's buffers are carved, and the session's
+// argument checks.  No HIP here (tests/host/plan_check.cpp compiles it
 // with a plain C++17 compiler); i7m_api.hip asks these selectors and only launches.
 #pragma once
 
 #include <algorithm>
+#include <cmath>
 #include <cstdlib>
 #include <cstring>
 #include <string>
@@ -326,6 +328,79 @@ inline void tracking_ws_bytes(int G, int H, int N, int num_steps, int n_endpoint
   bytes[TWS_REF] = 8 * (size_t)L * ref_stride;
   bytes[TWS_PHASE] = L > 0 && phase ? 4 * (size_t)G : 0;
   bytes[TWS_EE] = L > 0 ? 3 * 8 * history_rows(num_steps, G) : 0;
+}
+
+// ---- the controller session (i7m_ctrl_begin / i7m_ctrl_step / i7m_ctrl_end, i7m_ctrl.h) ----------
+
+// One group's record of a step, what a step's single device-to-host copy carries: the control, the
+// winning wrench, the tracking error, the EE position and the winner's index (as a double: < 256).
+enum { CREC_U = 0, CREC_FBEST = 6, CREC_ERR = 12, CREC_EE = 13, CREC_BEST = 16, CTRL_REC = 17 };
+// The session's device buffers, all allocated by i7m_ctrl_begin: the reference and the groups'
+// phases; per group XU_best, x_last, u_last and the scored hypothesis; the step's inputs (the
+// measurement, the noise) and its output records; the rows' initial rho (I7M_QP_ADMM resets).
+enum { CWS_REF, CWS_PHASE, CWS_XUB, CWS_XLAST, CWS_ULAST, CWS_BEST, CWS_XMEAS, CWS_NOISE, CWS_REC, CWS_RHO0,
+       CTRL_WS_COUNT };
+inline void ctrl_ws_bytes(int G, int H, int N, long L, int ref_stride, bool phase, size_t bytes[CTRL_WS_COUNT]) {
+  const size_t B = (size_t)G * H;
+  bytes[CWS_REF] = 8 * (size_t)L * ref_stride;
+  bytes[CWS_PHASE] = phase ? 4 * (size_t)G : 0;
+  bytes[CWS_XUB] = 8 * (18 * (size_t)N - 6) * G;
+  bytes[CWS_XLAST] = bytes[CWS_XMEAS] = 12 * 8 * (size_t)G;
+  bytes[CWS_ULAST] = 6 * 8 * (size_t)G;
+  bytes[CWS_BEST] = 4 * (size_t)G;
+  bytes[CWS_NOISE] = 3 * 8 * B;
+  bytes[CWS_REC] = CTRL_REC * 8 * (size_t)G;
+  bytes[CWS_RHO0] = 8 * B;
+}
+// The session's pinned host staging: the measurement and the noise on their way in, the records on
+// their way out.
+enum { CHS_XMEAS, CHS_NOISE, CHS_REC, CTRL_HS_COUNT };
+inline void ctrl_host_bytes(int G, int H, size_t bytes[CTRL_HS_COUNT]) {
+  bytes[CHS_XMEAS] = 12 * 8 * (size_t)G;
+  bytes[CHS_NOISE] = 3 * 8 * (size_t)G * H;
+  bytes[CHS_REC] = CTRL_REC * 8 * (size_t)G;
+}
+
+// i7m_ctrl_begin's arguments.  On a refusal *which names the argument and *at is the offending
+// value, or the entry for ref_phase (null pointers: 0).
+inline bool ctrl_begin_args_ok(int qp_mode, int max_batch, int G, int H, long L, int ref_stride, const void* ref,
+                               const int32_t* ref_phase, const void* fhyp, int frame, int reset_what,
+                               const char** which, long* at) {
+  const auto no = [&](const char* w, long a) {
+    *which = w;
+    *at = a;
+    return false;
+  };
+  if (qp_mode != I7M_QP_DIRECT && qp_mode != I7M_QP_ADMM) return no("qp_mode", qp_mode);
+  if (H < 1 || H > 256 || (H & (H - 1))) return no("H", H);
+  if (G < 0 || (long)G * H > max_batch) return no("G", (long)G * H);
+  if (L < 1) return no("L", L);
+  if (ref_stride != 3 && ref_stride != 6) return no("ref_stride", ref_stride);
+  if (frame != I7M_WRENCH_LOCAL && frame != I7M_WRENCH_WORLD) return no("frame", frame);
+  if (reset_what & ~I7M_ADMM_RESET_ALL) return no("reset_what", reset_what);
+  if (!ref) return no("ref", 0);
+  if (!fhyp) return no("fhyp", 0);
+  for (int g = 0; ref_phase && g < G; ++g)
+    if (ref_phase[g] < 0) return no("ref_phase", g);
+  return true;
+}
+// i7m_ctrl_step's: the pointers, the clock, the offset, and a host scan of the measurement (a real
+// sensor path must not poison the carried warm start).  *at: the non-finite entry of x_meas, the
+// negative offset, -1 for a null pointer, else 0.
+inline bool ctrl_step_args_ok(const double* x_meas, int G, double elapsed, int32_t ref_offset, const void* u_out,
+                              const char** which, long* at) {
+  const auto no = [&](const char* w, long a) {
+    *which = w;
+    *at = a;
+    return false;
+  };
+  if (!x_meas) return no("x_meas", -1);
+  if (!u_out) return no("u_out", -1);
+  if (!std::isfinite(elapsed) || !(elapsed > 0.0)) return no("elapsed", 0);
+  if (ref_offset < 0) return no("ref_offset", ref_offset);
+  for (long e = 0; e < 12L * G; ++e)
+    if (!std::isfinite(x_meas[e])) return no("x_meas", e);
+  return true;
 }
 
 }  // namespace i7m

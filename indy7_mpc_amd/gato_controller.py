@@ -1,0 +1,120 @@
+"""Drop-in for the reference's ``gato_controller.py``: ``GATO_Controller`` without ROS.  The deployed
+controller (gato_controller.py:144-250) gets a joint state from a robot or a simulator at wall-clock
+intervals, slides the goal window along the reference trajectory, solves ``batch_size`` wrench
+hypotheses, scores them against the measurement over the elapsed time, resamples them and returns
+one torque vector.  Here ``step(x_curr)`` is ``joint_callback`` and the whole step is one call into
+the library (``i7m_ctrl_step``): one copy in, two small kernels around the solve, one copy out.
+
+    ctrl = GATO_Controller(ref_traj, batch_size=16, N=64, dt=0.01, f_ext_std=10.0, f_ext_resample_std=2.0)
+    u = ctrl.step(x_curr)        # in the joint-state callback; publish u as the effort command
+
+What differs from the reference, on purpose:
+  * no ROS node, publishers or timers: the caller owns the transport and calls ``step``;
+    ``f_ext_actual`` and its clipped random walk (:236-239) belong to the simulator, not here;
+  * the hypotheses and the resampling noise come from ``numpy.random.default_rng(seed)`` with the
+    reference's shapes and zeroing (torques 0, row 0 zero, :77-83; (batch_size, 6) normals per step
+    with the torques dropped), as ``MPC_GATO_Batch_Sample`` draws them; the reference's global
+    ``np.random`` draw order is not reproduced;
+  * the EE position is the model's forward kinematics of the measured q, where the controller
+    reads it from the simulator's message (``msg.effort[0:3]``, :203);
+  * ties go to the lowest index, the device's rule, where the controller's ``<=`` (:115) takes the
+    highest; tied hypotheses are identical rows, so the trajectories are the same;
+  * a window that runs past the end of the reference holds its last point (the controller's slice
+    would come up short there);
+  * ``solve_times`` are the wall-clock seconds of the whole step, not the solver's own microseconds;
+  * everything is fp64 (the reference's batch_sqp solves in float);
+  * ``groups`` > 1 runs that many independent controllers on one handle, one state row each, all on
+    one clock; ``step`` then takes (groups, 12) and returns (groups, 6).
+"""
+from __future__ import annotations
+
+import time
+
+import numpy as np
+
+from . import _lib
+from .model import default_model
+
+_SIZES = (1, 2, 4, 8, 16, 32, 64, 128, 256)
+
+
+class GATO_Controller:
+    def __init__(self, ref_traj=None, batch_size=1, N=32, dt=0.01, f_ext_std=0.0, f_ext_resample_std=0.0, model=None,
+                 seed=None, qp_mode="admm", groups=1, device_id=0):
+        if ref_traj is None:
+            raise ValueError("ref_traj must be provided")
+        if batch_size not in _SIZES:
+            raise ValueError(f"Batch size {batch_size} not supported")
+        if qp_mode not in ("direct", "admm"):
+            raise ValueError("qp_mode must be 'direct' or 'admm'")
+        ref = np.asarray(ref_traj, float)
+        if ref.ndim == 1:
+            ref = ref.reshape(-1, 6)
+        if ref.ndim != 2 or ref.shape[1] not in (3, 6) or ref.shape[0] < 1:
+            raise ValueError("ref_traj must be flat with 6 entries per point, (L, 3) or (L, 6)")
+        self.ref_traj = ref
+        self.ref_traj_offset = 0
+        self.batch_size, self.N, self.dt, self.groups = int(batch_size), int(N), float(dt), int(groups)
+        self.nu, self.nx = 6, 12
+        self.config = f"dt:{self.dt}_batch_size:{self.batch_size}_N:{self.N}_f_ext_std:{f_ext_std}"
+        self.rng = np.random.default_rng(seed)
+        if f_ext_std != 0.0:  # gato_controller.py:77-83
+            self.f_ext_batch = self.rng.normal(0, f_ext_std, (self.batch_size, 6))
+            self.f_ext_batch[:, 3:] = 0.0
+            self.f_ext_batch[0] = 0.0
+        else:
+            self.f_ext_batch = np.zeros((self.batch_size, 6))
+        self.f_ext_resample_std = float(f_ext_resample_std)
+        self.resample_f_ext = self.f_ext_resample_std > 0.0  # :85
+        self._h = _lib.Handle(model or default_model(), N=self.N, dt=self.dt, max_batch=self.groups * self.batch_size,
+                              device_id=device_id, qp_mode=_lib.QP_ADMM if qp_mode == "admm" else _lib.QP_DIRECT)
+        # :174-185: the window at offset 0, the zero state, one solve, XU_best = row 0; x_last unset
+        self._h.ctrl_begin(ref, np.tile(self.f_ext_batch, (self.groups, 1)), x0=None, groups=self.groups, frame="world",
+                           reset_what=_lib.ADMM_RESET_ALL, keep_best=True, decay=0.97)
+        self._open = True
+        # stats (:188-193), one entry per step
+        self.dts, self.tracking_errors, self.ee_positions, self.ee_ref_positions = [], [], [], []
+        self.joint_positions, self.solve_times, self.best_ids, self.f_ext_best = [], [], [], []
+        self.last_time = time.time()
+
+    def step(self, x_curr, elapsed_time=None):
+        """joint_callback (:201-250) on the measured state x_curr (12,) (or (groups, 12)):
+        elapsed_time seconds since the previous state, None = the wall clock since the previous
+        call (:209-211).  Returns u_curr (6,) (or (groups, 6)), the torques to command."""
+        now = time.time()
+        elapsed = now - self.last_time if elapsed_time is None else float(elapsed_time)
+        x = np.asarray(x_curr, float).reshape(self.groups, self.nx)
+        offset = int(self.ref_traj_offset + elapsed / self.dt)  # :214-215
+        noise = None
+        if self.resample_f_ext:
+            noise = self.rng.normal(0, self.f_ext_resample_std, (self.groups * self.batch_size, 6))[:, :3]
+        t0 = time.perf_counter()
+        r = self._h.ctrl_step(x, elapsed, offset, noise=noise)
+        solve_time = time.perf_counter() - t0
+        # a refused step (a non-finite state, a clock that did not advance) changes nothing above
+        self.last_time = now
+        self.ref_traj_offset += elapsed / self.dt
+        self.dts.append(elapsed)
+        one = self.groups == 1
+        first = self.ref_traj[min(offset, len(self.ref_traj) - 1), :3]
+        self.tracking_errors.append(r["err"][0] if one else r["err"])
+        self.ee_positions.append(r["ee"][0] if one else r["ee"])
+        self.ee_ref_positions.append(first)
+        self.joint_positions.append(x[0, :6].copy() if one else x[:, :6].copy())
+        self.solve_times.append(solve_time)
+        self.best_ids.append(int(r["best"][0]) if one else r["best"])
+        self.f_ext_best.append(r["fbest"][0] if one else r["fbest"])
+        return r["u"][0] if one else r["u"]
+
+    def get_stats(self):
+        return {k: getattr(self, k) for k in ("dts", "tracking_errors", "ee_positions", "ee_ref_positions",
+                                              "joint_positions", "solve_times", "best_ids", "f_ext_best")}
+
+    def close(self):
+        """End the session: f_ext_batch becomes the final hypotheses (group 0's), XU_best the final
+        trajectories.  The handle stays, so a later ``step`` is refused by the library."""
+        if self._open:
+            end = self._h.ctrl_end()
+            self.f_ext_batch = end["fhyp"][:self.batch_size].copy()
+            self.XU_best = end["xu_best"]
+            self._open = False

@@ -21,7 +21,9 @@ What differs from the reference, on purpose:
 (``GATO_Controller.joint_callback``, gato_controller.py:201-250: the N-knot goal window slides along
 a reference trajectory, ``i7m_mpc_run_tracking``).  What differs from ``GATO_Controller``:
   * the plant is the device's rk4 step of ``sim_dt``, not MuJoCo at wall-clock intervals, so the
-    window's offset follows the schedule floor((i + 1) sim_dt / dt) (or the caller's);
+    window's offset follows the schedule floor((i + 1) sim_dt / dt) (or the caller's); for a plant
+    outside the device use ``indy7_mpc_amd.gato_controller.GATO_Controller`` (one step per call on
+    the measured state);
   * the first step scores the hypotheses with the initial solve's control, where the controller
     starts from u_last = 0 (:206);
   * ties go to the lowest index, the device's rule, where the controller's ``<=`` (:115) takes the
