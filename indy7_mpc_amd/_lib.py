@@ -232,8 +232,14 @@ def _f64(a, shape=None) -> np.ndarray:
     return a
 
 
-def _ptr(a: np.ndarray):
-    return a.ctypes.data_as(_DP)
+def _ptr(a):
+    """float64 array, or None for a null pointer"""
+    return None if a is None else a.ctypes.data_as(_DP)
+
+
+def _iptr(a):
+    """int32 array, or None"""
+    return None if a is None else a.ctypes.data_as(_IP32)
 
 
 class Handle:
@@ -411,7 +417,7 @@ class Handle:
         n = q.shape[0]
         p = np.empty((n, 3))
         J = np.empty((n, 3, NJ)) if jacobian else None
-        _check(self._lib.i7m_eepos(self._h, n, _ptr(q), _ptr(p), _ptr(J) if J is not None else None))
+        _check(self._lib.i7m_eepos(self._h, n, _ptr(q), _ptr(p), _ptr(J)))
         return (p, J) if jacobian else p
 
     def aba(self, q, v, tau, fext=None, frame="local"):
@@ -421,8 +427,7 @@ class Handle:
         n = q.shape[0]
         a = np.empty((n, NJ))
         f = _f64(fext).reshape(n, 6) if fext is not None else None
-        _check(self._lib.i7m_aba(self._h, n, _ptr(q), _ptr(v), _ptr(tau), _ptr(f) if f is not None else None,
-                                 _FRAMES[frame], _ptr(a)))
+        _check(self._lib.i7m_aba(self._h, n, _ptr(q), _ptr(v), _ptr(tau), _ptr(f), _FRAMES[frame], _ptr(a)))
         return a
 
     def aba_derivatives(self, q, v, tau):
@@ -441,8 +446,8 @@ class Handle:
         n = q.shape[0]
         qo, vo = np.empty((n, NJ)), np.empty((n, NJ))
         f = _f64(fext).reshape(n, 6) if fext is not None else None
-        _check(self._lib.i7m_rk4(self._h, n, _ptr(q), _ptr(v), _ptr(u), float(dt), _ptr(f) if f is not None else None,
-                                 _FRAMES[frame], _ptr(qo), _ptr(vo)))
+        _check(self._lib.i7m_rk4(self._h, n, _ptr(q), _ptr(v), _ptr(u), float(dt), _ptr(f), _FRAMES[frame], _ptr(qo),
+                                 _ptr(vo)))
         return qo, vo
 
     def mpc_run(self, xstart, endpoints, num_steps):
@@ -459,15 +464,48 @@ class Handle:
                                      _ptr(xc), _ptr(xu)))
         return d, q, xc, xu
 
+    # ---- the sampled-wrench family: what its three entry points parse the same way -------------
+    @staticmethod
+    def _hypotheses(fhyp, G):
+        """fhyp as (G * H, 6) and H."""
+        fh = _f64(fhyp).reshape(-1, 6)
+        if G < 1 or fh.shape[0] % G:
+            raise ValueError(f"fhyp has {fh.shape[0]} rows, not a multiple of the {G} groups")
+        return fh, fh.shape[0] // G
+
+    @staticmethod
+    def _reference(ref):
+        """ref as a 2-D array: its extents are L and the stride."""
+        rf = _f64(ref)
+        if rf.ndim != 2:
+            raise ValueError("ref must be (L, 3) or (L, 6)")
+        return rf
+
+    @staticmethod
+    def _phases(ref_phase, G):
+        """The groups' phases as a (G,) int32 array, or None."""
+        if ref_phase is None:
+            return None
+        rp = np.ascontiguousarray(ref_phase, dtype=np.int32).reshape(-1)
+        if rp.shape[0] != G:
+            raise ValueError(f"ref_phase must be ({G},)")
+        return rp
+
+    def _opts(self, frame, reset_what, keep_best, decay, sim_dt=None, n_actual=None):
+        """The options struct: the library's defaults, then the caller's."""
+        o = i7m_sampled_opts()
+        _check(self._lib.i7m_sampled_opts_default(C.byref(o)))
+        o.decay, o.frame, o.reset_what, o.keep_best = float(decay), _FRAMES[frame], int(reset_what), int(bool(keep_best))
+        if sim_dt is not None:
+            o.sim_dt, o.n_actual = float(sim_dt), int(n_actual)
+        return o
+
     def _sampled_inputs(self, xstart, num_steps, fhyp, f_actual, noise, sim_dt, frame, reset_what, keep_best, decay):
         """The arguments mpc_run_sampled and mpc_run_tracking share, as contiguous arrays and the
         options struct: (xs, G, fh, H, fa, noise or None, opts)."""
         xs = _f64(xstart).reshape(-1, NX)
         G = xs.shape[0]
-        fh = _f64(fhyp).reshape(-1, 6)
-        if G < 1 or fh.shape[0] % G:
-            raise ValueError(f"fhyp has {fh.shape[0]} rows, not a multiple of the {G} groups")
-        Hn = fh.shape[0] // G
+        fh, Hn = self._hypotheses(fhyp, G)
         fa = _f64(f_actual)
         if fa.size == G * 6:
             fa = fa.reshape(1, G, 6)
@@ -480,11 +518,7 @@ class Handle:
             nz = _f64(noise)
             if nz.size != num_steps * G * Hn * 3:
                 raise ValueError(f"noise must be ({num_steps}, {G * Hn}, 3)")
-        o = i7m_sampled_opts()
-        _check(self._lib.i7m_sampled_opts_default(C.byref(o)))
-        o.sim_dt, o.decay, o.frame = float(sim_dt), float(decay), _FRAMES[frame]
-        o.reset_what, o.keep_best, o.n_actual = int(reset_what), int(bool(keep_best)), fa.shape[0]
-        return xs, G, fh, Hn, fa, nz, o
+        return xs, G, fh, Hn, fa, nz, self._opts(frame, reset_what, keep_best, decay, sim_dt, fa.shape[0])
 
     def mpc_run_sampled(self, xstart, endpoints, num_steps, fhyp, f_actual, noise=None, sim_dt=0.001, frame="world",
                         reset_what=ADMM_RESET_ALL, keep_best=False, decay=1.0):
@@ -502,10 +536,9 @@ class Handle:
                    q=np.empty((num_steps, G, NJ)), fbest=np.empty((num_steps, G, 6)), xcur=np.empty((G, NX)),
                    xu_best=np.empty((G, self.T)), fhyp=np.empty((G * Hn, 6)))
         _check(self._lib.i7m_mpc_run_sampled(self._h, G, Hn, _ptr(xs), _ptr(ep), ep.shape[0], num_steps, _ptr(fh),
-                                             _ptr(fa), _ptr(nz) if nz is not None else None, C.byref(o),
-                                             _ptr(out["dist"]), out["best"].ctypes.data_as(_IP32), _ptr(out["q"]),
-                                             _ptr(out["fbest"]), _ptr(out["xcur"]), _ptr(out["xu_best"]),
-                                             _ptr(out["fhyp"])))
+                                             _ptr(fa), _ptr(nz), C.byref(o), _ptr(out["dist"]), _iptr(out["best"]),
+                                             _ptr(out["q"]), _ptr(out["fbest"]), _ptr(out["xcur"]),
+                                             _ptr(out["xu_best"]), _ptr(out["fhyp"])))
         return out
 
     def mpc_run_tracking(self, xstart, ref, ref_offset, fhyp, f_actual, ref_phase=None, noise=None, sim_dt=0.01,
@@ -517,27 +550,18 @@ class Handle:
         ref[min(phase[g] + ref_offset[i] + k, L - 1)], k = 0 .. N-1.  Returns a dict: err
         (num_steps, G) the distance of the EE to the window's first point, best, q, ee
         (num_steps, G, 3), fbest, xcur, xu_best, fhyp."""
-        rf = _f64(ref)
-        if rf.ndim != 2:
-            raise ValueError("ref must be (L, 3) or (L, 6)")
-        L, stride = rf.shape
+        rf = self._reference(ref)
         ro = np.ascontiguousarray(ref_offset, dtype=np.int32).reshape(-1)
         num_steps = ro.shape[0]
         xs, G, fh, Hn, fa, nz, o = self._sampled_inputs(xstart, num_steps, fhyp, f_actual, noise, sim_dt, frame,
                                                          reset_what, keep_best, decay)
-        rp = None
-        if ref_phase is not None:
-            rp = np.ascontiguousarray(ref_phase, dtype=np.int32).reshape(-1)
-            if rp.shape[0] != G:
-                raise ValueError(f"ref_phase must be ({G},)")
+        rp = self._phases(ref_phase, G)
         out = dict(err=np.empty((num_steps, G)), best=np.empty((num_steps, G), dtype=np.int32),
                    q=np.empty((num_steps, G, NJ)), ee=np.empty((num_steps, G, 3)), fbest=np.empty((num_steps, G, 6)),
                    xcur=np.empty((G, NX)), xu_best=np.empty((G, self.T)), fhyp=np.empty((G * Hn, 6)))
-        _check(self._lib.i7m_mpc_run_tracking(self._h, G, Hn, _ptr(xs), _ptr(rf), L, stride,
-                                              rp.ctypes.data_as(_IP32) if rp is not None else None,
-                                              ro.ctypes.data_as(_IP32), num_steps, _ptr(fh), _ptr(fa),
-                                              _ptr(nz) if nz is not None else None, C.byref(o), _ptr(out["err"]),
-                                              out["best"].ctypes.data_as(_IP32), _ptr(out["q"]), _ptr(out["ee"]),
+        _check(self._lib.i7m_mpc_run_tracking(self._h, G, Hn, _ptr(xs), _ptr(rf), *rf.shape, _iptr(rp), _iptr(ro),
+                                              num_steps, _ptr(fh), _ptr(fa), _ptr(nz), C.byref(o), _ptr(out["err"]),
+                                              _iptr(out["best"]), _ptr(out["q"]), _ptr(out["ee"]),
                                               _ptr(out["fbest"]), _ptr(out["xcur"]), _ptr(out["xu_best"]),
                                               _ptr(out["fhyp"])))
         return out
@@ -550,30 +574,17 @@ class Handle:
         with the returned control as u_last; x0 None: the controller's constructor (rows at the
         zero state, the first step scores from x_last = x_meas, u_last = 0), G = `groups` (default
         1).  fhyp (G * H, 6), ref_phase (G,) or None.  Returns u (G, 6), the initial solve's control."""
-        rf = _f64(ref)
-        if rf.ndim != 2:
-            raise ValueError("ref must be (L, 3) or (L, 6)")
-        L, stride = rf.shape
+        rf = self._reference(ref)
         xs = None if x0 is None else _f64(x0).reshape(-1, NX)
         G = int(groups) if groups is not None else (1 if xs is None else xs.shape[0])
         if xs is not None and xs.shape[0] != G:
             raise ValueError(f"x0 must be ({G}, 12)")
-        fh = _f64(fhyp).reshape(-1, 6)
-        if G < 1 or fh.shape[0] % G:
-            raise ValueError(f"fhyp has {fh.shape[0]} rows, not a multiple of the {G} groups")
-        Hn = fh.shape[0] // G
-        rp = None
-        if ref_phase is not None:
-            rp = np.ascontiguousarray(ref_phase, dtype=np.int32).reshape(-1)
-            if rp.shape[0] != G:
-                raise ValueError(f"ref_phase must be ({G},)")
-        o = i7m_sampled_opts()
-        _check(self._lib.i7m_sampled_opts_default(C.byref(o)))
-        o.decay, o.frame, o.reset_what, o.keep_best = float(decay), _FRAMES[frame], int(reset_what), int(bool(keep_best))
+        fh, Hn = self._hypotheses(fhyp, G)
+        rp = self._phases(ref_phase, G)
+        o = self._opts(frame, reset_what, keep_best, decay)
         u = np.empty((G, NU))
-        _check(self._lib.i7m_ctrl_begin(self._h, G, Hn, _ptr(xs) if xs is not None else None, _ptr(rf), L, stride,
-                                        rp.ctypes.data_as(_IP32) if rp is not None else None, _ptr(fh), C.byref(o),
-                                        _ptr(u)))
+        _check(self._lib.i7m_ctrl_begin(self._h, G, Hn, _ptr(xs), _ptr(rf), *rf.shape,
+                                        _iptr(rp), _ptr(fh), C.byref(o), _ptr(u)))
         self._ctrl = (G, Hn)
         return u
 
@@ -591,10 +602,8 @@ class Handle:
                 raise ValueError(f"noise must be ({G * Hn}, 3)")
         out = dict(u=np.empty((G, NU)), best=np.empty(G, dtype=np.int32), fbest=np.empty((G, 6)), err=np.empty(G),
                    ee=np.empty((G, 3)))
-        _check(self._lib.i7m_ctrl_step(self._h, _ptr(xm), float(elapsed), int(ref_offset),
-                                       _ptr(nz) if nz is not None else None, _ptr(out["u"]),
-                                       out["best"].ctypes.data_as(_IP32), _ptr(out["fbest"]), _ptr(out["err"]),
-                                       _ptr(out["ee"])))
+        _check(self._lib.i7m_ctrl_step(self._h, _ptr(xm), float(elapsed), int(ref_offset), _ptr(nz), _ptr(out["u"]),
+                                       _iptr(out["best"]), _ptr(out["fbest"]), _ptr(out["err"]), _ptr(out["ee"])))
         return out
 
     def ctrl_end(self):

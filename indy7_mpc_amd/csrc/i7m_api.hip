@@ -84,6 +84,27 @@ struct Timing {
 
 }  // namespace
 
+// One allocation carved into 256-byte aligned sub-buffers (carve, i7m_plan.h): device memory, or
+// pinned host memory.  Its owner releases it once nothing queued still uses it.
+struct Carved {
+  char* base = nullptr;
+  bool pinned = false;
+  std::vector<size_t> off;
+  bool alloc(const size_t* bytes, int n, bool pinned_host) {
+    off.resize(n);
+    const size_t total = std::max(carve(bytes, n, off.data()), WS_ALIGN);
+    pinned = pinned_host;
+    const hipError_t e = pinned ? hipHostMalloc((void**)&base, total, hipHostMallocDefault) : hipMalloc((void**)&base, total);
+    if (e != hipSuccess) base = nullptr;
+    return base != nullptr;
+  }
+  void release() {
+    if (base) (void)(pinned ? hipHostFree(base) : hipFree(base));
+    base = nullptr;
+  }
+  template <class P> P* at(int i) const { return reinterpret_cast<P*>(base + off[i]); }
+};
+
 // A controller session (i7m_ctrl_begin .. i7m_ctrl_end): one device allocation and one pinned host
 // allocation, carved by i7m_plan.h's ctrl_ws_bytes / ctrl_host_bytes, and what the steps carry.
 struct CtrlSession {
@@ -91,11 +112,8 @@ struct CtrlSession {
   int G = 0, H = 0;
   bool have_last = false;  // x_last / u_last are set (i7m_ctrl_begin with x0, or a step has run)
   i7m_sampled_opts o{};
-  char *dev = nullptr, *host = nullptr;
-  size_t doff[CTRL_WS_COUNT] = {}, hoff[CTRL_HS_COUNT] = {};
+  Carved dev, host;
   CtrlArgs a{};  // the launches' arguments, all but the step's own (elapsed, off, noise, have_last, initial)
-  template <class P> P* d(int i) const { return reinterpret_cast<P*>(dev + doff[i]); }
-  template <class P> P* p(int i) const { return reinterpret_cast<P*>(host + hoff[i]); }
 };
 
 struct i7m_handle {
@@ -268,8 +286,8 @@ bool dev_alloc(i7m_handle* h, P** p, size_t bytes) {
 // The controller session's two allocations back (i7m_ctrl_end, i7m_destroy); nothing queued may
 // still use them.
 void ctrl_release(i7m_handle* h) {
-  if (h->ctrl.dev) (void)hipFree(h->ctrl.dev);
-  if (h->ctrl.host) (void)hipHostFree(h->ctrl.host);
+  h->ctrl.dev.release();
+  h->ctrl.host.release();
   h->ctrl = CtrlSession{};
 }
 
@@ -957,24 +975,20 @@ int admm_reset_rows(i7m_handle* h, long lo, long n, int what, hipStream_t s, con
   return I7M_OK;
 }
 
-// One closed-loop call's device memory beyond the handle's: one allocation carved into 256-byte
-// aligned sub-buffers (carve, i7m_plan.h).  The destructor synchronises the handle's stream before
-// it frees, so on every return, error or not, nothing queued still uses the memory.
-struct Workspace {
+// One closed-loop call's device memory beyond the handle's: a Carved (base null: the allocation
+// failed) whose destructor synchronises the handle's stream before it frees, so on every return,
+// error or not, nothing queued still uses the memory.
+struct Workspace : Carved {
   i7m_handle* h;
-  char* base = nullptr;  // null: the allocation failed
-  std::vector<size_t> off;
   template <size_t NB>
-  Workspace(i7m_handle* hh, const size_t (&bytes)[NB]) : h(hh), off(NB) {
-    const size_t total = carve(bytes, (int)NB, off.data());
-    if (hipMalloc((void**)&base, total ? total : WS_ALIGN) != hipSuccess) base = nullptr;
+  Workspace(i7m_handle* hh, const size_t (&bytes)[NB]) : h(hh) {
+    alloc(bytes, (int)NB, false);
   }
   Workspace(const Workspace&) = delete;
   ~Workspace() {
     (void)hipStreamSynchronize(h->stream);
-    if (base) (void)hipFree(base);
+    release();
   }
-  template <class P> P* at(int i) const { return reinterpret_cast<P*>(base + off[i]); }
 };
 
 // The start of a closed loop on the handle's stream (src/osqp_mpc.py:14-27,
@@ -1000,14 +1014,66 @@ struct LoopStart {
         goals[b * W + e] = ref[track_index(ref_phase ? ref_phase[b / H] : 0, 0, (long)(e / 3), L) * ref_stride + e % 3];
   }
 };
+int loop_instances(i7m_handle* h, const LoopStart& st, const double* endpoints, int n_endpoints, double* d_ep, int* d_gi,
+                   int* d_alive) {
+  const int rc = copy_in(h, d_ep, endpoints, 3 * (size_t)n_endpoints);
+  if (rc) return rc;
+  HIPCHK(hipMemsetAsync(d_gi, 0, 4 * st.ones.size(), h->stream));
+  HIPCHK(hipMemcpyAsync(d_alive, st.ones.data(), 4 * st.ones.size(), hipMemcpyHostToDevice, h->stream));
+  return I7M_OK;
+}
 int loop_start(i7m_handle* h, const LoopStart& st, const double* endpoints, int n_endpoints, double* d_ep, int* d_gi,
                int* d_alive) {
   int rc;
   if ((rc = copy_in(h, h->d_goal, st.goals.data(), st.goals.size()))) return rc;
-  if ((rc = copy_in(h, d_ep, endpoints, 3 * (size_t)n_endpoints))) return rc;
-  HIPCHK(hipMemsetAsync(d_gi, 0, 4 * st.ones.size(), h->stream));
-  HIPCHK(hipMemcpyAsync(d_alive, st.ones.data(), 4 * st.ones.size(), hipMemcpyHostToDevice, h->stream));
+  if ((rc = loop_instances(h, st, endpoints, n_endpoints, d_ep, d_gi, d_alive))) return rc;
   HIPCHK(hipMemsetAsync(h->d_xu, 0, 8 * st.rows * h->T, h->stream));
+  return I7M_OK;
+}
+
+// The start of the sampled-wrench family (the loops, the controller session): G groups of H rows,
+// every row of group g at state x[g], or at the zero state where x is null.  The host staging of
+// the goal rows, the rows' states and their initial rho; the caller keeps it until its synchronize.
+struct GroupStart {
+  LoopStart rows;
+  std::vector<double> xrows, rho0;
+  GroupStart(const i7m_handle* h, int G, int H, const double* x, const GoalSource& gs)
+      : rows(gs.ref ? LoopStart(h, (size_t)G * H, G, H, gs.ref, gs.L, gs.ref_stride, gs.ref_phase)
+                    : LoopStart(h, (size_t)G * H, G, gs.endpoints)),
+        xrows((size_t)G * H * 12, 0.0), rho0((size_t)G * H, h->cfg.admm_rho) {
+    for (size_t b = 0; x && b < rho0.size(); ++b)
+      for (int r = 0; r < 12; ++r) xrows[b * 12 + r] = x[(b / H) * 12 + r];
+  }
+};
+// Queues it on the handle's stream: d_xs, the goal rows, XU = [x, 0...], the rows' rho into d_rho0
+// and, for a tracking source, the reference into d_ref and the groups' phases into d_phase (null
+// without phases).
+int stage_start(i7m_handle* h, const GroupStart& st, const GoalSource& gs, int G, double* d_rho0, double* d_ref,
+                int* d_phase) {
+  const size_t T = h->T, B = st.rho0.size();
+  int rc;
+  if ((rc = copy_in(h, h->d_xs, st.xrows.data(), st.xrows.size()))) return rc;
+  if ((rc = copy_in(h, h->d_goal, st.rows.goals.data(), st.rows.goals.size()))) return rc;
+  HIPCHK(hipMemsetAsync(h->d_xu, 0, 8 * B * T, h->stream));
+  if (B > 0)
+    HIPCHK(hipMemcpy2DAsync(h->d_xu, T * 8, st.xrows.data(), 12 * 8, 12 * 8, B, hipMemcpyHostToDevice, h->stream));
+  if ((rc = copy_in(h, d_rho0, st.rho0.data(), B))) return rc;
+  if (gs.ref && (rc = copy_in(h, d_ref, gs.ref, (size_t)gs.L * gs.ref_stride))) return rc;
+  if (d_phase) HIPCHK(hipMemcpyAsync(d_phase, gs.ref_phase, 4 * (size_t)G, hipMemcpyHostToDevice, h->stream));
+  return I7M_OK;
+}
+
+// The joint-6 wrenches of rows [0, B) (host, frame `frame`) as the handle's, the rows beyond them
+// zero.  The handle's flags change, and the captured graphs (which hold the wrench kernel choice) go,
+// only once the copy is known to have landed.
+int install_wrench(i7m_handle* h, int B, const double* fext, int frame) {
+  HIPCHK(hipMemsetAsync(h->d_fext, 0, (size_t)h->cfg.max_batch * 6 * 8, h->stream));
+  const int rc = copy_in(h, h->d_fext, fext, (size_t)B * 6);
+  if (rc) return rc;
+  HIPCHK(hipStreamSynchronize(h->stream));
+  h->has_fext = true;
+  h->fext_frame = frame;
+  drop_graphs(h);
   return I7M_OK;
 }
 
@@ -1296,14 +1362,7 @@ int i7m_set_external_wrench(i7m_handle* h, int32_t B, const double* fext, int32_
     return fail(I7M_EINVAL, "frame must be I7M_WRENCH_LOCAL or I7M_WRENCH_WORLD");
   if (B < 1 || B > h->cfg.max_batch) return fail(I7M_EINVAL, "external wrench batch outside [1, max_batch]");
   HIPCHK(hipSetDevice(h->dev));
-  HIPCHK(hipMemsetAsync(h->d_fext, 0, (size_t)h->cfg.max_batch * 6 * 8, h->stream));
-  HIPCHK(hipMemcpyAsync(h->d_fext, fext, (size_t)B * 6 * 8, hipMemcpyHostToDevice, h->stream));
-  HIPCHK(hipStreamSynchronize(h->stream));
-  h->has_fext = true;
-  h->fext_frame = frame;
-  // captured graphs hold the old wrench pointer / kernel choice
-  drop_graphs(h);
-  return I7M_OK;
+  return install_wrench(h, B, fext, frame);
 }
 
 int i7m_reset(i7m_handle* h) {
@@ -1621,61 +1680,48 @@ int i7m_sampled_opts_default(i7m_sampled_opts* o) {
 
 namespace {
 
-// The goal source of the sampled loop: the endpoints (i7m_mpc_run_sampled) or, with ref set, a
-// reference trajectory and the caller's window schedule (i7m_mpc_run_tracking).
-struct GoalSource {
-  const double* endpoints = nullptr;  // (n_endpoints, 3)
-  int n_endpoints = 0;
-  const double* ref = nullptr;  // (L, ref_stride)
-  long L = 0;
-  int ref_stride = 0;
-  const int32_t* ref_phase = nullptr;   // (G) or null
-  const int32_t* ref_offset = nullptr;  // (num_steps)
-};
+// The description of a call of the sampled-wrench family on this handle (i7m_plan.h).
+SampledCall describe_call(const i7m_handle* h, SampledKind kind, int G, int H, int num_steps, const i7m_sampled_opts* opts,
+                          const GoalSource& goal, const double* xstart, const double* fhyp, const double* f_actual,
+                          const double* hist_out) {
+  SampledCall c;
+  c.kind = kind;
+  c.qp_mode = h->cfg.qp_mode;
+  c.max_batch = h->cfg.max_batch;
+  c.dt = h->cfg.dt;
+  c.G = G;
+  c.H = H;
+  c.num_steps = num_steps;
+  (void)i7m_sampled_opts_default(&c.o);
+  if (opts) c.o = *opts;
+  c.goal = goal;
+  c.xstart = xstart;
+  c.fhyp = fhyp;
+  c.f_actual = f_actual;
+  c.hist_out = hist_out;
+  return c;
+}
+// The family's one argument check (sampled_call_ok), before the device is touched and before any
+// handle state changes.
+int check_call(const std::string& who, const SampledCall& c) {
+  const char* which = "";
+  long at = 0;
+  if (sampled_call_ok(c, &which, &at)) return I7M_OK;
+  return fail(I7M_EINVAL, sampled_refusal(who, which, at, c.max_batch));
+}
 
 // The sampled-wrench closed loop of both entry points (`who` names the one in the messages).
 // ee_out: the tracking mode's EE history, null in endpoint mode.
-int sampled_loop(i7m_handle* h, const std::string& who, bool track, int32_t G, int32_t H, const double* xstart,
-                 const GoalSource& gs, int32_t num_steps, const double* fhyp, const double* f_actual, const double* noise,
-                 const i7m_sampled_opts* opts, double* dist_out, int32_t* best_out, double* q_out, double* ee_out,
-                 double* fbest_out, double* xcur_out, double* xu_best_out, double* fhyp_out) {
-  if (!h) return fail(I7M_EINVAL, "null handle");
+int sampled_loop(i7m_handle* h, const std::string& who, const SampledCall& c, const double* noise, double* dist_out,
+                 int32_t* best_out, double* q_out, double* ee_out, double* fbest_out, double* xcur_out,
+                 double* xu_best_out, double* fhyp_out) {
   if (h->ctrl.open) return session_open();
-  i7m_sampled_opts o;
-  (void)i7m_sampled_opts_default(&o);
-  if (opts) o = *opts;
-  if (h->cfg.qp_mode == I7M_QP_BOX)
-    return fail(I7M_EINVAL, who + ": I7M_QP_BOX is not supported (I7M_QP_DIRECT or I7M_QP_ADMM)");
-  if (H < 1 || H > 256 || (H & (H - 1)))
-    return fail(I7M_EINVAL, who + ": H = " + std::to_string(H) + " is not one of 1, 2, 4, ..., 256");
-  if (G < 0 || (long)G * H > h->cfg.max_batch)
-    return fail(I7M_EINVAL, who + ": G x H = " + std::to_string((long)G * H) + " rows outside [0, max_batch=" +
-                                std::to_string(h->cfg.max_batch) + "]");
-  if (!(o.sim_dt > 0.0) || !(o.sim_dt <= h->cfg.dt)) return fail(I7M_EINVAL, who + ": sim_dt must be in (0, dt]");
-  if (o.frame != I7M_WRENCH_LOCAL && o.frame != I7M_WRENCH_WORLD)
-    return fail(I7M_EINVAL, who + ": frame must be I7M_WRENCH_LOCAL or I7M_WRENCH_WORLD");
-  if (o.reset_what & ~I7M_ADMM_RESET_ALL) return fail(I7M_EINVAL, who + ": unknown I7M_ADMM_RESET_* bits");
-  if (!track) {
-    if (gs.n_endpoints < 1 || num_steps < 0) return fail(I7M_EINVAL, who + ": need >= 1 endpoint, num_steps >= 0");
-  } else {
-    if (num_steps < 0) return fail(I7M_EINVAL, who + ": need num_steps >= 0");
-    if (gs.L < 1) return fail(I7M_EINVAL, who + ": L = " + std::to_string(gs.L) + ", the reference needs >= 1 point");
-    if (gs.ref_stride != 3 && gs.ref_stride != 6)
-      return fail(I7M_EINVAL, who + ": ref_stride = " + std::to_string(gs.ref_stride) + " is not 3 or 6");
-  }
-  if (o.n_actual != 1 && o.n_actual != num_steps) return fail(I7M_EINVAL, who + ": n_actual must be 1 or num_steps");
-  if (!track) {
-    if (!xstart || !gs.endpoints || !fhyp || !f_actual || !dist_out)
-      return fail(I7M_EINVAL, who + ": null xstart, endpoints, fhyp, f_actual or dist_out");
-  } else {
-    if (!xstart || !gs.ref || !fhyp || !f_actual || !dist_out)
-      return fail(I7M_EINVAL, who + ": null xstart, ref, fhyp, f_actual or err_out");
-    if (num_steps > 0 && !gs.ref_offset) return fail(I7M_EINVAL, who + ": null ref_offset with num_steps > 0");
-    const char* which = "";
-    int at = 0;
-    if (!track_schedule_ok(gs.ref_phase, G, gs.ref_offset, num_steps, &which, &at))
-      return fail(I7M_EINVAL, who + ": " + which + "[" + std::to_string(at) + "] is negative");
-  }
+  int rc;
+  if ((rc = check_call(who, c))) return rc;
+  const int G = c.G, H = c.H, num_steps = c.num_steps;
+  const i7m_sampled_opts& o = c.o;
+  const GoalSource& gs = c.goal;
+  const bool track = c.kind == SampledKind::tracking;
   if (G == 0) return I7M_OK;
   HIPCHK(hipSetDevice(h->dev));
   const int N = (int)h->N, B = G * H;
@@ -1688,9 +1734,7 @@ int sampled_loop(i7m_handle* h, const std::string& who, bool track, int32_t G, i
   tracking_ws_bytes(G, H, N, num_steps, gs.n_endpoints, o.n_actual, noise != nullptr, gs.L, gs.ref_stride,
                     gs.ref_phase != nullptr, bytes);
   // host staging, declared first: alive until the workspace's final synchronize
-  const LoopStart start = track ? LoopStart(h, B, G, H, gs.ref, gs.L, gs.ref_stride, gs.ref_phase)
-                                : LoopStart(h, B, G, gs.endpoints);
-  std::vector<double> xrows((size_t)B * 12), rho0((size_t)B, h->cfg.admm_rho);
+  const GroupStart start(h, G, H, c.xstart, gs);
   Workspace ws(h, bytes);
   if (!ws.base) return fail(I7M_ENOMEM, who + ": device allocation failed");
   double *d_ep = ws.at<double>(SWS_EP), *d_xcur = ws.at<double>(SWS_XCUR), *d_xub = ws.at<double>(SWS_XUB),
@@ -1704,25 +1748,13 @@ int sampled_loop(i7m_handle* h, const std::string& who, bool track, int32_t G, i
   // src/gato_mpc_batch_sample.py:111-128: goal = endpoint 0 tiled (tracking: the window at offset
   // 0), XU = [xstart, 0...], every row of a group at the group's start state, the hypotheses set
   // on the solver
-  for (size_t b = 0; b < (size_t)B; ++b)
-    for (int r = 0; r < 12; ++r) xrows[b * 12 + r] = xstart[(b / H) * 12 + r];
-  int rc;
-  if ((rc = copy_in(h, h->d_xs, xrows.data(), xrows.size()))) return rc;
-  if ((rc = copy_in(h, d_xcur, xstart, (size_t)G * 12))) return rc;
-  if ((rc = loop_start(h, start, gs.endpoints, gs.n_endpoints, d_ep, d_gi, d_alive))) return rc;
-  if (track && (rc = copy_in(h, d_ref, gs.ref, (size_t)gs.L * gs.ref_stride))) return rc;
-  if (d_phase) HIPCHK(hipMemcpyAsync(d_phase, gs.ref_phase, 4 * (size_t)G, hipMemcpyHostToDevice, h->stream));
-  if ((rc = copy_in(h, d_fact, f_actual, 6 * (size_t)o.n_actual * G))) return rc;
+  if ((rc = stage_start(h, start, gs, G, d_rho0, d_ref, d_phase))) return rc;
+  if ((rc = loop_instances(h, start.rows, gs.endpoints, gs.n_endpoints, d_ep, d_gi, d_alive))) return rc;
+  if ((rc = copy_in(h, d_xcur, c.xstart, (size_t)G * 12))) return rc;
+  if ((rc = copy_in(h, d_fact, c.f_actual, 6 * (size_t)o.n_actual * G))) return rc;
   if (d_noise && (rc = copy_in(h, d_noise, noise, 3 * (size_t)num_steps * B))) return rc;
-  if ((rc = copy_in(h, d_rho0, rho0.data(), rho0.size()))) return rc;
-  HIPCHK(hipMemcpy2DAsync(h->d_xu, T * 8, xrows.data(), 12 * 8, 12 * 8, (size_t)B, hipMemcpyHostToDevice, h->stream));
   HIPCHK(hipMemsetAsync(d_best, 0, 4 * (size_t)G, h->stream));  // the initial solve's XU_best is row 0, :128
-  HIPCHK(hipMemsetAsync(h->d_fext, 0, (size_t)h->cfg.max_batch * 6 * 8, h->stream));
-  if ((rc = copy_in(h, h->d_fext, fhyp, (size_t)B * 6))) return rc;
-  HIPCHK(hipStreamSynchronize(h->stream));
-  h->has_fext = true;
-  h->fext_frame = o.frame;
-  drop_graphs(h);  // captured graphs hold the old wrench kernel choice
+  if ((rc = install_wrench(h, B, c.fhyp, o.frame))) return rc;
   // the rows [lo, lo + n) (whole groups) through every MPC step on stream s, as i7m_mpc_run's
   // ranges: the groups are independent, so a staggered range runs its steps on its own
   rc = run_ranges(h, B, [&](long lo, int n, hipStream_t s, StaggerMark* mark) -> int {
@@ -1803,11 +1835,11 @@ int i7m_mpc_run_sampled(i7m_handle* h, int32_t G, int32_t H, const double* xstar
                         int32_t n_endpoints, int32_t num_steps, const double* fhyp, const double* f_actual,
                         const double* noise, const i7m_sampled_opts* opts, double* dist_out, int32_t* best_out,
                         double* q_out, double* fbest_out, double* xcur_out, double* xu_best_out, double* fhyp_out) {
-  GoalSource gs;
-  gs.endpoints = endpoints;
-  gs.n_endpoints = n_endpoints;
-  return sampled_loop(h, "mpc_run_sampled", false, G, H, xstart, gs, num_steps, fhyp, f_actual, noise, opts, dist_out,
-                      best_out, q_out, nullptr, fbest_out, xcur_out, xu_best_out, fhyp_out);
+  if (!h) return fail(I7M_EINVAL, "null handle");
+  const SampledCall c = describe_call(h, SampledKind::endpoints, G, H, num_steps, opts,
+                                      GoalSource::of_endpoints(endpoints, n_endpoints), xstart, fhyp, f_actual, dist_out);
+  return sampled_loop(h, "mpc_run_sampled", c, noise, dist_out, best_out, q_out, nullptr, fbest_out, xcur_out,
+                      xu_best_out, fhyp_out);
 }
 
 int i7m_mpc_run_tracking(i7m_handle* h, int32_t G, int32_t H, const double* xstart, const double* ref, int32_t L,
@@ -1815,36 +1847,17 @@ int i7m_mpc_run_tracking(i7m_handle* h, int32_t G, int32_t H, const double* xsta
                          const double* fhyp, const double* f_actual, const double* noise, const i7m_sampled_opts* opts,
                          double* err_out, int32_t* best_out, double* q_out, double* ee_out, double* fbest_out,
                          double* xcur_out, double* xu_best_out, double* fhyp_out) {
-  GoalSource gs;
-  gs.ref = ref;
-  gs.L = L;
-  gs.ref_stride = ref_stride;
-  gs.ref_phase = ref_phase;
-  gs.ref_offset = ref_offset;
-  return sampled_loop(h, "mpc_run_tracking", true, G, H, xstart, gs, num_steps, fhyp, f_actual, noise, opts, err_out,
-                      best_out, q_out, ee_out, fbest_out, xcur_out, xu_best_out, fhyp_out);
+  if (!h) return fail(I7M_EINVAL, "null handle");
+  const SampledCall c = describe_call(h, SampledKind::tracking, G, H, num_steps, opts,
+                                      GoalSource::of_reference(ref, L, ref_stride, ref_phase, ref_offset), xstart, fhyp,
+                                      f_actual, err_out);
+  return sampled_loop(h, "mpc_run_tracking", c, noise, err_out, best_out, q_out, ee_out, fbest_out, xcur_out,
+                      xu_best_out, fhyp_out);
 }
 
 }  // extern "C"
 
 namespace {
-
-// The message of a refusal by ctrl_begin_args_ok / ctrl_step_args_ok (i7m_plan.h).
-std::string ctrl_refusal(const i7m_handle* h, const std::string& who, const std::string& which, long at) {
-  const std::string v = std::to_string(at);
-  if (which == "qp_mode") return who + ": I7M_QP_BOX is not supported (I7M_QP_DIRECT or I7M_QP_ADMM)";
-  if (which == "H") return who + ": H = " + v + " is not one of 1, 2, 4, ..., 256";
-  if (which == "G") return who + ": G x H = " + v + " rows outside [0, max_batch=" + std::to_string(h->cfg.max_batch) + "]";
-  if (which == "L") return who + ": L = " + v + ", the reference needs >= 1 point";
-  if (which == "ref_stride") return who + ": ref_stride = " + v + " is not 3 or 6";
-  if (which == "frame") return who + ": frame must be I7M_WRENCH_LOCAL or I7M_WRENCH_WORLD";
-  if (which == "reset_what") return who + ": reset_what has unknown I7M_ADMM_RESET_* bits";
-  if (which == "ref_phase") return who + ": ref_phase[" + v + "] is negative";
-  if (which == "elapsed") return who + ": elapsed must be finite and > 0";
-  if (which == "ref_offset") return who + ": ref_offset = " + v + " is negative";
-  if (which == "x_meas" && at >= 0) return who + ": x_meas[" + v + "] is not finite";
-  return who + ": null " + which;
-}
 
 // The session's solve: opts->reset_what on every row (I7M_QP_ADMM), then the rows' SQP from XU into
 // d_out, one range on the handle's stream.
@@ -1853,7 +1866,7 @@ int ctrl_solve(i7m_handle* h, int what) {
   const int B = c.G * c.H;
   int rc;
   if (h->cfg.qp_mode == I7M_QP_ADMM && what &&
-      (rc = admm_reset_rows(h, 0, B, what, h->stream, c.d<double>(CWS_RHO0), hipMemcpyDeviceToDevice)))
+      (rc = admm_reset_rows(h, 0, B, what, h->stream, c.dev.at<double>(CWS_RHO0), hipMemcpyDeviceToDevice)))
     return rc;
   return run_sqp(h, B, h->d_xu, h->d_out, h->d_xs, h->d_goal, 3, nullptr);
 }
@@ -1872,28 +1885,24 @@ int i7m_ctrl_begin(i7m_handle* h, int32_t G, int32_t H, const double* x0, const 
   const std::string who = "ctrl_begin";
   if (!h) return fail(I7M_EINVAL, "null handle");
   if (h->ctrl.open) return fail(I7M_EINVAL, who + ": a controller session is already open on this handle");
-  i7m_sampled_opts o;
-  (void)i7m_sampled_opts_default(&o);
-  if (opts) o = *opts;
-  const char* which = "";
-  long at = 0;
-  if (!ctrl_begin_args_ok(h->cfg.qp_mode, h->cfg.max_batch, G, H, L, ref_stride, ref, ref_phase, fhyp, o.frame,
-                          o.reset_what, &which, &at))
-    return fail(I7M_EINVAL, ctrl_refusal(h, who, which, at));
+  const SampledCall call = describe_call(h, SampledKind::session, G, H, 0, opts,
+                                         GoalSource::of_reference(ref, L, ref_stride, ref_phase, nullptr), x0, fhyp, nullptr,
+                                         nullptr);
+  int rc;
+  if ((rc = check_call(who, call))) return rc;
+  const i7m_sampled_opts& o = call.o;
   HIPCHK(hipSetDevice(h->dev));
   HIPCHK(hipStreamSynchronize(h->stream));
-  const int N = (int)h->N, B = G * H;
-  const size_t T = h->T;
+  const int N = (int)h->N;
   CtrlSession& c = h->ctrl;
   size_t db[CTRL_WS_COUNT], hb[CTRL_HS_COUNT];
   ctrl_ws_bytes(G, H, N, L, ref_stride, ref_phase != nullptr, db);
   ctrl_host_bytes(G, H, hb);
-  const size_t dtotal = carve(db, CTRL_WS_COUNT, c.doff), htotal = carve(hb, CTRL_HS_COUNT, c.hoff);
-  if (hipMalloc((void**)&c.dev, dtotal ? dtotal : WS_ALIGN) != hipSuccess) {
+  if (!c.dev.alloc(db, CTRL_WS_COUNT, false)) {
     ctrl_release(h);
     return fail(I7M_ENOMEM, who + ": device allocation failed");
   }
-  if (hipHostMalloc((void**)&c.host, htotal ? htotal : WS_ALIGN, hipHostMallocDefault) != hipSuccess) {
+  if (!c.host.alloc(hb, CTRL_HS_COUNT, true)) {
     ctrl_release(h);
     return fail(I7M_ENOMEM, who + ": pinned host allocation failed");
   }
@@ -1912,40 +1921,26 @@ int i7m_ctrl_begin(i7m_handle* h, int32_t G, int32_t H, const double* x0, const 
   a.xu_new = h->d_out;
   a.goals = h->d_goal;
   a.fext = h->d_fext;
-  a.x_meas = c.d<double>(CWS_XMEAS);
-  a.x_last = c.d<double>(CWS_XLAST);
-  a.u_last = c.d<double>(CWS_ULAST);
-  a.xub = c.d<double>(CWS_XUB);
-  a.best = c.d<int>(CWS_BEST);
-  a.rec = c.d<double>(CWS_REC);
-  a.ref = c.d<double>(CWS_REF);
-  a.ref_phase = ref_phase ? c.d<int>(CWS_PHASE) : nullptr;
+  a.x_meas = c.dev.at<double>(CWS_XMEAS);
+  a.x_last = c.dev.at<double>(CWS_XLAST);
+  a.u_last = c.dev.at<double>(CWS_ULAST);
+  a.xub = c.dev.at<double>(CWS_XUB);
+  a.best = c.dev.at<int>(CWS_BEST);
+  a.rec = c.dev.at<double>(CWS_REC);
+  a.ref = c.dev.at<double>(CWS_REF);
+  a.ref_phase = ref_phase ? c.dev.at<int>(CWS_PHASE) : nullptr;
   a.L = L;
   a.ref_stride = ref_stride;
   // gato_controller.py:174-185: the window at offset 0, XU = [x0, 0...] (x0 NULL: the zero state),
   // the hypotheses set on the solver, its state afresh, one solve, XU_best = row 0 of every group
-  const LoopStart start(h, B, G, H, ref, L, ref_stride, ref_phase);
-  std::vector<double> xrows((size_t)B * 12, 0.0), rho0((size_t)B, h->cfg.admm_rho);
-  for (size_t b = 0; x0 && b < (size_t)B; ++b)
-    for (int r = 0; r < 12; ++r) xrows[b * 12 + r] = x0[(b / H) * 12 + r];
-  int rc = I7M_OK;
+  const GroupStart start(h, G, H, x0, call.goal);
   const auto stage = [&]() -> int {
     int r;
-    if ((r = copy_in(h, c.d<double>(CWS_REF), ref, (size_t)L * ref_stride))) return r;
-    if (ref_phase) HIPCHK(hipMemcpyAsync(c.d<int>(CWS_PHASE), ref_phase, 4 * (size_t)G, hipMemcpyHostToDevice, h->stream));
-    if ((r = copy_in(h, c.d<double>(CWS_RHO0), rho0.data(), rho0.size()))) return r;
-    if (x0 && (r = copy_in(h, c.d<double>(CWS_XMEAS), x0, (size_t)G * 12))) return r;
-    if ((r = copy_in(h, h->d_goal, start.goals.data(), start.goals.size()))) return r;
-    if ((r = copy_in(h, h->d_xs, xrows.data(), xrows.size()))) return r;
-    HIPCHK(hipMemsetAsync(h->d_xu, 0, 8 * (size_t)B * T, h->stream));
-    if (B > 0)
-      HIPCHK(hipMemcpy2DAsync(h->d_xu, T * 8, xrows.data(), 12 * 8, 12 * 8, (size_t)B, hipMemcpyHostToDevice, h->stream));
-    HIPCHK(hipMemsetAsync(h->d_fext, 0, (size_t)h->cfg.max_batch * 6 * 8, h->stream));
-    if ((r = copy_in(h, h->d_fext, fhyp, (size_t)B * 6))) return r;
-    HIPCHK(hipStreamSynchronize(h->stream));
-    h->has_fext = true;
-    h->fext_frame = o.frame;
-    drop_graphs(h);  // captured graphs hold the old wrench kernel choice
+    if ((r = stage_start(h, start, call.goal, G, c.dev.at<double>(CWS_RHO0), c.dev.at<double>(CWS_REF),
+                         ref_phase ? c.dev.at<int>(CWS_PHASE) : nullptr)))
+      return r;
+    if (x0 && (r = copy_in(h, c.dev.at<double>(CWS_XMEAS), x0, (size_t)G * 12))) return r;
+    if ((r = install_wrench(h, G * H, fhyp, o.frame))) return r;
     if (G == 0) return I7M_OK;
     if ((r = ctrl_solve(h, I7M_ADMM_RESET_ALL))) return r;
     CtrlArgs s = a;
@@ -1954,7 +1949,7 @@ int i7m_ctrl_begin(i7m_handle* h, int32_t G, int32_t H, const double* x0, const 
     s.x_meas = x0 ? a.x_meas : nullptr;
     ctrl_launch_select(h, s);
     HIPCHK(hipGetLastError());
-    if ((r = copy_out(h, c.p<double>(CHS_REC), a.rec, (size_t)G * CTRL_REC))) return r;
+    if ((r = copy_out(h, c.host.at<double>(CHS_REC), a.rec, (size_t)G * CTRL_REC))) return r;
     HIPCHK(hipStreamSynchronize(h->stream));
     return I7M_OK;
   };
@@ -1966,7 +1961,7 @@ int i7m_ctrl_begin(i7m_handle* h, int32_t G, int32_t H, const double* x0, const 
     return rc;
   }
   for (int g = 0; u_out && g < G; ++g)
-    for (int k = 0; k < 6; ++k) u_out[6 * g + k] = c.p<double>(CHS_REC)[(size_t)g * CTRL_REC + CREC_U + k];
+    for (int k = 0; k < 6; ++k) u_out[6 * g + k] = c.host.at<double>(CHS_REC)[(size_t)g * CTRL_REC + CREC_U + k];
   c.open = true;
   return I7M_OK;
 }
@@ -1980,24 +1975,24 @@ int i7m_ctrl_step(i7m_handle* h, const double* x_meas, double elapsed, int32_t r
   const char* which = "";
   long at = 0;
   if (!ctrl_step_args_ok(x_meas, c.G, elapsed, ref_offset, u_out, &which, &at))
-    return fail(I7M_EINVAL, ctrl_refusal(h, who, which, at));
+    return fail(I7M_EINVAL, ctrl_step_refusal(who, which, at));
   if (c.G == 0) return I7M_OK;
   HIPCHK(hipSetDevice(h->dev));
   const size_t G = c.G, B = G * c.H;
   // the whole step as one range on the handle's stream: copy-in, measure, reset, solve, select, one
   // copy-out, one synchronisation
-  double *px = c.p<double>(CHS_XMEAS), *pn = c.p<double>(CHS_NOISE), *pr = c.p<double>(CHS_REC);
+  double *px = c.host.at<double>(CHS_XMEAS), *pn = c.host.at<double>(CHS_NOISE), *pr = c.host.at<double>(CHS_REC);
   std::memcpy(px, x_meas, 8 * 12 * G);
   if (noise) std::memcpy(pn, noise, 8 * 3 * B);
   int rc;
-  if ((rc = copy_in(h, c.d<double>(CWS_XMEAS), px, 12 * G))) return rc;
-  if (noise && (rc = copy_in(h, c.d<double>(CWS_NOISE), pn, 3 * B))) return rc;
+  if ((rc = copy_in(h, c.dev.at<double>(CWS_XMEAS), px, 12 * G))) return rc;
+  if (noise && (rc = copy_in(h, c.dev.at<double>(CWS_NOISE), pn, 3 * B))) return rc;
   CtrlArgs a = c.a;
   a.elapsed = elapsed;
   a.off = ref_offset;
   a.have_last = c.have_last;
   a.initial = 0;
-  a.noise = noise ? c.d<double>(CWS_NOISE) : nullptr;
+  a.noise = noise ? c.dev.at<double>(CWS_NOISE) : nullptr;
   hipLaunchKernelGGL(k_ctrl_measure, dim3(c.G), dim3((c.H + 63) / 64 * 64), 0, h->stream, h->d_model, a);
   HIPCHK(hipGetLastError());
   if ((rc = ctrl_solve(h, c.o.reset_what))) return rc;

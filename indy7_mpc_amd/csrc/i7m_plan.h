@@ -1,8 +1,8 @@
 // i7m_plan.h — the launch plan of libindy7mpc.so as pure host code: which kernel variant a launch
 // of a given size runs, whether a batch staggers, where its ranges and chunks begin, and how a
-// closed loop's per-call workspace and a controller session's buffers are carved, and the session's
-// argument checks.  No HIP here (tests/host/plan_check.cpp compiles it
-// with a plain C++17 compiler); i7m_api.hip asks these selectors and only launches.
+// closed loop's per-call workspace and a controller session's buffers are carved, and the argument
+// check and refusal messages of the sampled-wrench entry points.  No HIP here (tests/host/ compiles
+// it with a plain C++17 compiler); i7m_api.hip asks these selectors and only launches.
 #pragma once
 
 #include <algorithm>
@@ -300,24 +300,6 @@ I7M_PLAN_HD inline long track_index(long ph, long off, long k, long L) {
   const long i = ph + off + k;
   return i < L - 1 ? i : L - 1;
 }
-// The caller's schedule: every phase (G of them, or none) and every offset >= 0.  On a refusal
-// *which names the argument and *at the entry.
-inline bool track_schedule_ok(const int32_t* ref_phase, int G, const int32_t* ref_offset, int num_steps,
-                              const char** which, int* at) {
-  for (int g = 0; ref_phase && g < G; ++g)
-    if (ref_phase[g] < 0) {
-      *which = "ref_phase";
-      *at = g;
-      return false;
-    }
-  for (int i = 0; i < num_steps; ++i)
-    if (ref_offset[i] < 0) {
-      *which = "ref_offset";
-      *at = i;
-      return false;
-    }
-  return true;
-}
 // The sampled loop's request with either goal source: sampled_ws_bytes' 13 sub-buffers, then the
 // reference (L, ref_stride), the groups' phases and the EE history.  Endpoint mode (L = 0): those
 // three are empty and take no room, so its allocation is what it was.
@@ -361,29 +343,105 @@ inline void ctrl_host_bytes(int G, int H, size_t bytes[CTRL_HS_COUNT]) {
   bytes[CHS_REC] = CTRL_REC * 8 * (size_t)G;
 }
 
-// i7m_ctrl_begin's arguments.  On a refusal *which names the argument and *at is the offending
-// value, or the entry for ref_phase (null pointers: 0).
-inline bool ctrl_begin_args_ok(int qp_mode, int max_batch, int G, int H, long L, int ref_stride, const void* ref,
-                               const int32_t* ref_phase, const void* fhyp, int frame, int reset_what,
-                               const char** which, long* at) {
+// ---- a call of the sampled-wrench family: its description, its one check, its refusal texts -------
+
+// The goal source: the endpoints (i7m_mpc_run_sampled) or a reference trajectory and the caller's
+// window schedule (i7m_mpc_run_tracking; i7m_ctrl_begin, whose offsets come with the steps).
+struct GoalSource {
+  const double* endpoints = nullptr;  // (n_endpoints, 3)
+  int n_endpoints = 0;
+  const double* ref = nullptr;  // (L, ref_stride)
+  long L = 0;
+  int ref_stride = 0;
+  const int32_t* ref_phase = nullptr;   // (G) or null
+  const int32_t* ref_offset = nullptr;  // (num_steps)
+  static GoalSource of_endpoints(const double* endpoints, int n_endpoints) {
+    GoalSource g;
+    g.endpoints = endpoints;
+    g.n_endpoints = n_endpoints;
+    return g;
+  }
+  static GoalSource of_reference(const double* ref, long L, int ref_stride, const int32_t* ref_phase,
+                                 const int32_t* ref_offset) {
+    GoalSource g;
+    g.ref = ref;
+    g.L = L;
+    g.ref_stride = ref_stride;
+    g.ref_phase = ref_phase;
+    g.ref_offset = ref_offset;
+    return g;
+  }
+};
+// A call of i7m_mpc_run_sampled (endpoints), i7m_mpc_run_tracking (tracking) or i7m_ctrl_begin
+// (session): the handle's part, the sizes, the options, the goal source and the caller's required
+// pointers (hist_out: dist_out / err_out).  The session has no steps and reads neither sim_dt nor
+// n_actual; its start states are optional.
+enum class SampledKind { endpoints, tracking, session };
+struct SampledCall {
+  SampledKind kind = SampledKind::endpoints;
+  int qp_mode = I7M_QP_DIRECT, max_batch = 0;
+  double dt = 0.0;
+  int G = 0, H = 0, num_steps = 0;
+  i7m_sampled_opts o{};
+  GoalSource goal;
+  const double *xstart = nullptr, *fhyp = nullptr, *f_actual = nullptr;
+  const double* hist_out = nullptr;
+};
+// The one argument check of the family, host reads only.  On a refusal *which names the argument
+// and *at is the offending value; the entry for ref_phase and ref_offset; 0 for a null pointer (-1
+// for a null ref_offset, whose entry 0 can be negative too).  The scans read G phases and num_steps
+// offsets, no more: no groups reads no phases.
+inline bool sampled_call_ok(const SampledCall& c, const char** which, long* at) {
   const auto no = [&](const char* w, long a) {
     *which = w;
     *at = a;
     return false;
   };
-  if (qp_mode != I7M_QP_DIRECT && qp_mode != I7M_QP_ADMM) return no("qp_mode", qp_mode);
-  if (H < 1 || H > 256 || (H & (H - 1))) return no("H", H);
-  if (G < 0 || (long)G * H > max_batch) return no("G", (long)G * H);
-  if (L < 1) return no("L", L);
-  if (ref_stride != 3 && ref_stride != 6) return no("ref_stride", ref_stride);
-  if (frame != I7M_WRENCH_LOCAL && frame != I7M_WRENCH_WORLD) return no("frame", frame);
-  if (reset_what & ~I7M_ADMM_RESET_ALL) return no("reset_what", reset_what);
-  if (!ref) return no("ref", 0);
-  if (!fhyp) return no("fhyp", 0);
-  for (int g = 0; ref_phase && g < G; ++g)
-    if (ref_phase[g] < 0) return no("ref_phase", g);
+  const bool loop = c.kind != SampledKind::session, track = c.kind != SampledKind::endpoints;
+  const GoalSource& g = c.goal;
+  if (c.qp_mode != I7M_QP_DIRECT && c.qp_mode != I7M_QP_ADMM) return no("qp_mode", c.qp_mode);
+  if (c.H < 1 || c.H > 256 || (c.H & (c.H - 1))) return no("H", c.H);
+  if (c.G < 0 || (long)c.G * c.H > c.max_batch) return no("G", (long)c.G * c.H);
+  if (loop && (!(c.o.sim_dt > 0.0) || !(c.o.sim_dt <= c.dt))) return no("sim_dt", 0);
+  if (c.o.frame != I7M_WRENCH_LOCAL && c.o.frame != I7M_WRENCH_WORLD) return no("frame", c.o.frame);
+  if (c.o.reset_what & ~I7M_ADMM_RESET_ALL) return no("reset_what", c.o.reset_what);
+  if (!track && g.n_endpoints < 1) return no("n_endpoints", g.n_endpoints);
+  if (c.num_steps < 0) return no("num_steps", c.num_steps);
+  if (track && g.L < 1) return no("L", g.L);
+  if (track && g.ref_stride != 3 && g.ref_stride != 6) return no("ref_stride", g.ref_stride);
+  if (loop && c.o.n_actual != 1 && c.o.n_actual != c.num_steps) return no("n_actual", c.o.n_actual);
+  if (loop && !c.xstart) return no("xstart", 0);
+  if (!track && !g.endpoints) return no("endpoints", 0);
+  if (track && !g.ref) return no("ref", 0);
+  if (!c.fhyp) return no("fhyp", 0);
+  if (loop && !c.f_actual) return no("f_actual", 0);
+  if (loop && !c.hist_out) return no(track ? "err_out" : "dist_out", 0);
+  if (loop && track && c.num_steps > 0 && !g.ref_offset) return no("ref_offset", -1);
+  for (int i = 0; track && g.ref_phase && i < c.G; ++i)
+    if (g.ref_phase[i] < 0) return no("ref_phase", i);
+  for (int i = 0; loop && track && i < c.num_steps; ++i)
+    if (g.ref_offset[i] < 0) return no("ref_offset", i);
   return true;
 }
+// The text of a refusal by sampled_call_ok, for the entry point `who`.
+inline std::string sampled_refusal(const std::string& who, const std::string& which, long at, int max_batch) {
+  const std::string v = std::to_string(at);
+  if (which == "qp_mode") return who + ": I7M_QP_BOX is not supported (I7M_QP_DIRECT or I7M_QP_ADMM)";
+  if (which == "H") return who + ": H = " + v + " is not one of 1, 2, 4, ..., 256";
+  if (which == "G") return who + ": G x H = " + v + " rows outside [0, max_batch=" + std::to_string(max_batch) + "]";
+  if (which == "sim_dt") return who + ": sim_dt must be in (0, dt]";
+  if (which == "frame") return who + ": frame must be I7M_WRENCH_LOCAL or I7M_WRENCH_WORLD";
+  if (which == "reset_what") return who + ": reset_what has unknown I7M_ADMM_RESET_* bits";
+  if (which == "n_endpoints") return who + ": n_endpoints = " + v + ", need >= 1 endpoint";
+  if (which == "num_steps") return who + ": num_steps = " + v + ", need num_steps >= 0";
+  if (which == "L") return who + ": L = " + v + ", the reference needs >= 1 point";
+  if (which == "ref_stride") return who + ": ref_stride = " + v + " is not 3 or 6";
+  if (which == "n_actual") return who + ": n_actual must be 1 or num_steps";
+  if (which == "ref_offset" && at < 0) return who + ": null ref_offset with num_steps > 0";
+  if (which == "ref_phase" || which == "ref_offset") return who + ": " + which + "[" + v + "] is negative";
+  return who + ": null " + which;
+}
+
 // i7m_ctrl_step's: the pointers, the clock, the offset, and a host scan of the measurement (a real
 // sensor path must not poison the carried warm start).  *at: the non-finite entry of x_meas, the
 // negative offset, -1 for a null pointer, else 0.
@@ -401,6 +459,14 @@ inline bool ctrl_step_args_ok(const double* x_meas, int G, double elapsed, int32
   for (long e = 0; e < 12L * G; ++e)
     if (!std::isfinite(x_meas[e])) return no("x_meas", e);
   return true;
+}
+// The text of a refusal by ctrl_step_args_ok.
+inline std::string ctrl_step_refusal(const std::string& who, const std::string& which, long at) {
+  const std::string v = std::to_string(at);
+  if (which == "elapsed") return who + ": elapsed must be finite and > 0";
+  if (which == "ref_offset") return who + ": ref_offset = " + v + " is negative";
+  if (which == "x_meas" && at >= 0) return who + ": x_meas[" + v + "] is not finite";
+  return who + ": null " + which;
 }
 
 }  // namespace i7m

@@ -32,10 +32,8 @@ import time
 
 import numpy as np
 
-from . import _lib
+from . import _lib, _sampling
 from .model import default_model
-
-_SIZES = (1, 2, 4, 8, 16, 32, 64, 128, 256)
 
 
 class GATO_Controller:
@@ -43,31 +41,18 @@ class GATO_Controller:
                  seed=None, qp_mode="admm", groups=1, device_id=0):
         if ref_traj is None:
             raise ValueError("ref_traj must be provided")
-        if batch_size not in _SIZES:
-            raise ValueError(f"Batch size {batch_size} not supported")
-        if qp_mode not in ("direct", "admm"):
-            raise ValueError("qp_mode must be 'direct' or 'admm'")
-        ref = np.asarray(ref_traj, float)
-        if ref.ndim == 1:
-            ref = ref.reshape(-1, 6)
-        if ref.ndim != 2 or ref.shape[1] not in (3, 6) or ref.shape[0] < 1:
-            raise ValueError("ref_traj must be flat with 6 entries per point, (L, 3) or (L, 6)")
-        self.ref_traj = ref
+        mode = _sampling.qp_mode_of(batch_size, qp_mode)
+        self.ref_traj = ref = _sampling.reference_points(ref_traj)
         self.ref_traj_offset = 0
         self.batch_size, self.N, self.dt, self.groups = int(batch_size), int(N), float(dt), int(groups)
         self.nu, self.nx = 6, 12
         self.config = f"dt:{self.dt}_batch_size:{self.batch_size}_N:{self.N}_f_ext_std:{f_ext_std}"
         self.rng = np.random.default_rng(seed)
-        if f_ext_std != 0.0:  # gato_controller.py:77-83
-            self.f_ext_batch = self.rng.normal(0, f_ext_std, (self.batch_size, 6))
-            self.f_ext_batch[:, 3:] = 0.0
-            self.f_ext_batch[0] = 0.0
-        else:
-            self.f_ext_batch = np.zeros((self.batch_size, 6))
+        self.f_ext_batch = _sampling.initial_hypotheses(self.rng, self.batch_size, f_ext_std)
         self.f_ext_resample_std = float(f_ext_resample_std)
         self.resample_f_ext = self.f_ext_resample_std > 0.0  # :85
         self._h = _lib.Handle(model or default_model(), N=self.N, dt=self.dt, max_batch=self.groups * self.batch_size,
-                              device_id=device_id, qp_mode=_lib.QP_ADMM if qp_mode == "admm" else _lib.QP_DIRECT)
+                              device_id=device_id, qp_mode=mode)
         # :174-185: the window at offset 0, the zero state, one solve, XU_best = row 0; x_last unset
         self._h.ctrl_begin(ref, np.tile(self.f_ext_batch, (self.groups, 1)), x0=None, groups=self.groups, frame="world",
                            reset_what=_lib.ADMM_RESET_ALL, keep_best=True, decay=0.97)
@@ -87,7 +72,7 @@ class GATO_Controller:
         offset = int(self.ref_traj_offset + elapsed / self.dt)  # :214-215
         noise = None
         if self.resample_f_ext:
-            noise = self.rng.normal(0, self.f_ext_resample_std, (self.groups * self.batch_size, 6))[:, :3]
+            noise = _sampling.resampling_noise(self.rng, self.f_ext_resample_std, self.groups * self.batch_size)
         t0 = time.perf_counter()
         r = self._h.ctrl_step(x, elapsed, offset, noise=noise)
         solve_time = time.perf_counter() - t0

@@ -38,10 +38,8 @@ from fractions import Fraction
 
 import numpy as np
 
-from . import _lib
+from . import _lib, _sampling
 from .model import default_model
-
-_SIZES = (1, 2, 4, 8, 16, 32, 64, 128, 256)
 
 
 def tracking_schedule(sim_dt, sim_time, dt):
@@ -59,24 +57,15 @@ class MPC_GATO_Batch_Sample:
     def __init__(self, model=None, N=32, dt=0.01, batch_size=4, constant_f_ext=None, resample_f_ext=False,
                  f_ext_std=1.0, f_ext_resample_std=2.0, seed=None, qp_mode="admm", keep_best=False, decay=1.0,
                  device_id=0):
-        if batch_size not in _SIZES:
-            raise ValueError(f"Batch size {batch_size} not supported")
-        if qp_mode not in ("direct", "admm"):
-            raise ValueError("qp_mode must be 'direct' or 'admm'")
+        self.qp_mode = _sampling.qp_mode_of(batch_size, qp_mode)
         self.model = model or default_model()
         self.N, self.dt, self.batch_size = int(N), float(dt), int(batch_size)
-        self.qp_mode = _lib.QP_ADMM if qp_mode == "admm" else _lib.QP_DIRECT
         self.device_id = device_id
         self.resample_f_ext = bool(resample_f_ext)
         self.f_ext_resample_std = float(f_ext_resample_std)
         self.keep_best, self.decay = bool(keep_best), float(decay)
         self.rng = np.random.default_rng(seed)
-        if f_ext_std != 0.0:  # src/gato_mpc_batch_sample.py:37-40
-            self.f_ext_batch = self.rng.normal(0, f_ext_std, (self.batch_size, 6))
-            self.f_ext_batch[:, 3:] = 0.0
-            self.f_ext_batch[0] = 0.0
-        else:
-            self.f_ext_batch = np.zeros((self.batch_size, 6))
+        self.f_ext_batch = _sampling.initial_hypotheses(self.rng, self.batch_size, f_ext_std)
         self.actual_f_ext = np.zeros(6)
         if constant_f_ext is not None:
             self.actual_f_ext[:3] = np.asarray(constant_f_ext, float).reshape(-1)[:3]
@@ -91,6 +80,17 @@ class MPC_GATO_Batch_Sample:
             self._cap = rows
         return self._h
 
+    def _run_inputs(self, G, num_steps, f_actual):
+        """What both loops start from: the actual wrenches as (G, 6) or the caller's schedule, the
+        run's resampling noise (or None) and the handle."""
+        fa = np.tile(self.actual_f_ext, (G, 1)) if f_actual is None else np.asarray(f_actual, float)
+        if fa.size == 6:
+            fa = np.tile(fa.reshape(6), (G, 1))
+        noise = None
+        if self.resample_f_ext:
+            noise = _sampling.resampling_noise(self.rng, self.f_ext_resample_std, num_steps, G * self.batch_size)
+        return fa, noise, self._handle(G * self.batch_size)
+
     def run_mpc_groups(self, xstarts, endpoints, sim_dt=0.001, sim_time=5, f_actual=None):
         """G independent controllers, one per row of xstarts (G, 12), each with this object's
         hypotheses and its own resampling noise.  f_actual: (6,), (G, 6) or (num_steps, G, 6)
@@ -100,13 +100,7 @@ class MPC_GATO_Batch_Sample:
         xs = np.asarray(xstarts, float).reshape(-1, 12)
         G, H = xs.shape[0], self.batch_size
         num_steps = int(sim_time / sim_dt)
-        fa = np.tile(self.actual_f_ext, (G, 1)) if f_actual is None else np.asarray(f_actual, float)
-        if fa.size == 6:
-            fa = np.tile(fa.reshape(6), (G, 1))
-        noise = None
-        if self.resample_f_ext:  # (batch_size, 6) normals per step, torques dropped, :294-296
-            noise = self.rng.normal(0, self.f_ext_resample_std, (num_steps, G * H, 6))[:, :, :3]
-        h = self._handle(G * H)
+        fa, noise, h = self._run_inputs(G, num_steps, f_actual)
         t0 = time.perf_counter()
         r = h.mpc_run_sampled(xs, endpoints, num_steps, np.tile(self.f_ext_batch, (G, 1)), fa, noise=noise,
                               sim_dt=sim_dt, frame="world", reset_what=_lib.ADMM_RESET_ALL, keep_best=self.keep_best,
@@ -139,23 +133,13 @@ class MPC_GATO_Batch_Sample:
         (num_steps, G, 6), solve_times) plus 'best_ids' and 'f_ext_best'."""
         xs = np.asarray(xstarts, float).reshape(-1, 12)
         G, H = xs.shape[0], self.batch_size
-        ref = np.asarray(ref_traj, float)
-        if ref.ndim == 1:
-            ref = ref.reshape(-1, 6)
-        if ref.ndim != 2 or ref.shape[1] not in (3, 6) or ref.shape[0] < 1:
-            raise ValueError("ref_traj must be flat with 6 entries per point, (L, 3) or (L, 6)")
+        ref = _sampling.reference_points(ref_traj)
         if ref_offset is None:
             num_steps, ref_offset = tracking_schedule(sim_dt, sim_time, self.dt)
         ref_offset = np.asarray(ref_offset, dtype=np.int32).reshape(-1)
         num_steps = len(ref_offset)
         phase = np.zeros(G, np.int32) if ref_phase is None else np.asarray(ref_phase, dtype=np.int32).reshape(G)
-        fa = np.tile(self.actual_f_ext, (G, 1)) if f_actual is None else np.asarray(f_actual, float)
-        if fa.size == 6:
-            fa = np.tile(fa.reshape(6), (G, 1))
-        noise = None
-        if self.resample_f_ext:
-            noise = self.rng.normal(0, self.f_ext_resample_std, (num_steps, G * H, 6))[:, :, :3]
-        h = self._handle(G * H)
+        fa, noise, h = self._run_inputs(G, num_steps, f_actual)
         t0 = time.perf_counter()
         r = h.mpc_run_tracking(xs, ref, ref_offset, np.tile(self.f_ext_batch, (G, 1)), fa, ref_phase=phase, noise=noise,
                                sim_dt=sim_dt, frame="world", reset_what=_lib.ADMM_RESET_ALL, keep_best=self.keep_best,

@@ -1,6 +1,8 @@
 // Host check of the controller session's plan (indy7_mpc_amd/csrc/i7m_plan.h): the buffer request
-// of i7m_ctrl_begin against hand-computed bytes (ctrl_ws_bytes, ctrl_host_bytes, the record layout)
-// and the argument checks of i7m_ctrl_begin / i7m_ctrl_step (ctrl_begin_args_ok, ctrl_step_args_ok).
+// of i7m_ctrl_begin against hand-computed bytes (ctrl_ws_bytes, ctrl_host_bytes, the record layout),
+// the one argument check of the sampled-wrench family (sampled_call_ok: i7m_mpc_run_sampled,
+// i7m_mpc_run_tracking, i7m_ctrl_begin) with its refusal texts (sampled_refusal), and i7m_ctrl_step's
+// (ctrl_step_args_ok, ctrl_step_refusal).
 #include <cmath>
 #include <cstdio>
 #include <limits>
@@ -65,11 +67,24 @@ int main() {
   long at = -7;
   const double ref[6] = {0}, fh[6] = {0};
   const int32_t ph_ok[3] = {0, 17, 50}, ph_bad[3] = {0, 17, -2};
-  const auto begin = [&](int mode, int mb, int G, int H, long L, int stride, const void* r, const int32_t* ph, const void* f,
-                         int frame, int what) {
+  const auto begin = [&](int mode, int mb, int G, int H, long L, int stride, const double* r, const int32_t* ph,
+                         const double* f, int frame, int what) {
     which = "";
     at = -7;
-    return ctrl_begin_args_ok(mode, mb, G, H, L, stride, r, ph, f, frame, what, &which, &at);
+    SampledCall c;
+    c.kind = SampledKind::session;
+    c.qp_mode = mode;
+    c.max_batch = mb;
+    c.G = G;
+    c.H = H;
+    c.o.frame = frame;
+    c.o.reset_what = what;
+    c.goal.ref = r;
+    c.goal.L = L;
+    c.goal.ref_stride = stride;
+    c.goal.ref_phase = ph;
+    c.fhyp = f;
+    return sampled_call_ok(c, &which, &at);
   };
   const auto named = [&](const char* w, long a) { return std::string(which) == w && at == a; };
   CHECK(begin(I7M_QP_DIRECT, 12, 3, 4, 300, 6, ref, ph_ok, fh, I7M_WRENCH_WORLD, I7M_ADMM_RESET_ALL), "a valid begin");
@@ -92,6 +107,162 @@ int main() {
   CHECK(!begin(I7M_QP_DIRECT, 12, 3, 4, 300, 6, nullptr, nullptr, fh, 1, 7) && named("ref", 0), "null ref: %s", which);
   CHECK(!begin(I7M_QP_DIRECT, 12, 3, 4, 300, 6, ref, nullptr, nullptr, 1, 7) && named("fhyp", 0), "null fhyp: %s", which);
   CHECK(!begin(I7M_QP_DIRECT, 12, 3, 4, 300, 6, ref, ph_bad, fh, 1, 7) && named("ref_phase", 2), "phase: %s %ld", which, at);
+
+  // the two loops through the same check: a valid call of each, then one bad argument at a time
+  const double xs[36] = {0}, ends[6] = {0}, fa[18] = {0};
+  double hist[12];
+  const std::vector<int32_t> ph3 = {0, 17, 50}, off4 = {0, 0, 1, 2};  // heap arrays of exactly G and num_steps entries
+  const auto loop_call = [&](SampledKind kind) {
+    SampledCall c;
+    c.kind = kind;
+    c.qp_mode = I7M_QP_ADMM;
+    c.max_batch = 12;
+    c.dt = 0.01;
+    c.G = 3;
+    c.H = 4;
+    c.num_steps = 4;
+    c.o.sim_dt = 0.001;
+    c.o.decay = 1.0;
+    c.o.frame = I7M_WRENCH_WORLD;
+    c.o.reset_what = I7M_ADMM_RESET_ALL;
+    c.o.keep_best = 0;
+    c.o.n_actual = 1;
+    if (kind == SampledKind::endpoints) {
+      c.goal.endpoints = ends;
+      c.goal.n_endpoints = 2;
+    } else {
+      c.goal.ref = ref;
+      c.goal.L = 300;
+      c.goal.ref_stride = 6;
+      c.goal.ref_phase = ph3.data();
+      c.goal.ref_offset = off4.data();
+    }
+    c.xstart = xs;
+    c.fhyp = fh;
+    c.f_actual = fa;
+    c.hist_out = hist;
+    return c;
+  };
+  const auto ok = [&](const SampledCall& c) {
+    which = "";
+    at = -7;
+    return sampled_call_ok(c, &which, &at);
+  };
+  for (SampledKind kind : {SampledKind::endpoints, SampledKind::tracking}) {
+    const bool track = kind == SampledKind::tracking;
+    const SampledCall good = loop_call(kind);
+    SampledCall c = good;
+    CHECK(ok(c), "a valid loop call (tracking %d): %s %ld", (int)track, which, at);
+    c.qp_mode = I7M_QP_BOX;
+    CHECK(!ok(c) && named("qp_mode", I7M_QP_BOX), "loop box: %s %ld", which, at);
+    c = good, c.H = 3;
+    CHECK(!ok(c) && named("H", 3), "loop H: %s %ld", which, at);
+    c = good, c.G = 4;
+    CHECK(!ok(c) && named("G", 16), "loop rows: %s %ld", which, at);
+    // sim_dt in (0, dt], dt itself accepted
+    c = good, c.o.sim_dt = c.dt;
+    CHECK(ok(c), "sim_dt == dt refused: %s", which);
+    for (double sd : {0.0, -0.001, 0.011, std::numeric_limits<double>::quiet_NaN()}) {
+      c = good, c.o.sim_dt = sd;
+      CHECK(!ok(c) && std::string(which) == "sim_dt", "sim_dt %g: %s", sd, which);
+    }
+    c = good, c.o.frame = 5;
+    CHECK(!ok(c) && named("frame", 5), "loop frame: %s %ld", which, at);
+    c = good, c.o.reset_what = 8;
+    CHECK(!ok(c) && named("reset_what", 8), "loop reset: %s %ld", which, at);
+    // n_actual in {1, num_steps}
+    c = good, c.o.n_actual = 4;
+    CHECK(ok(c), "n_actual == num_steps refused: %s", which);
+    for (int na : {0, 2, 3, 5, -1}) {
+      c = good, c.o.n_actual = na;
+      CHECK(!ok(c) && named("n_actual", na), "n_actual %d: %s %ld", na, which, at);
+    }
+    c = good, c.num_steps = -1;
+    CHECK(!ok(c) && named("num_steps", -1), "negative num_steps: %s %ld", which, at);
+    // no steps: n_actual 1 only, and no offsets read
+    c = good, c.num_steps = 0, c.goal.ref_offset = nullptr;
+    CHECK(ok(c), "no steps refused: %s %ld", which, at);
+    // each required pointer
+    c = good, c.xstart = nullptr;
+    CHECK(!ok(c) && named("xstart", 0), "null xstart: %s %ld", which, at);
+    c = good, c.fhyp = nullptr;
+    CHECK(!ok(c) && named("fhyp", 0), "null fhyp: %s %ld", which, at);
+    c = good, c.f_actual = nullptr;
+    CHECK(!ok(c) && named("f_actual", 0), "null f_actual: %s %ld", which, at);
+    c = good, c.hist_out = nullptr;
+    CHECK(!ok(c) && named(track ? "err_out" : "dist_out", 0), "null history: %s %ld", which, at);
+    if (!track) {
+      c = good, c.goal.endpoints = nullptr;
+      CHECK(!ok(c) && named("endpoints", 0), "null endpoints: %s %ld", which, at);
+      for (int ne : {0, -1}) {
+        c = good, c.goal.n_endpoints = ne;
+        CHECK(!ok(c) && named("n_endpoints", ne), "n_endpoints %d: %s %ld", ne, which, at);
+      }
+      c = good, c.goal.n_endpoints = 1;
+      CHECK(ok(c), "one endpoint refused: %s", which);
+      // the endpoint loop reads nothing of a reference
+      c = good, c.goal.L = 0, c.goal.ref_stride = 4, c.goal.ref_phase = ph_bad;
+      CHECK(ok(c), "the endpoint loop looked at the reference: %s", which);
+    } else {
+      c = good, c.goal.ref = nullptr;
+      CHECK(!ok(c) && named("ref", 0), "loop null ref: %s %ld", which, at);
+      c = good, c.goal.ref_offset = nullptr;
+      CHECK(!ok(c) && named("ref_offset", -1), "null ref_offset with steps: %s %ld", which, at);
+      c = good, c.goal.L = 0;
+      CHECK(!ok(c) && named("L", 0), "loop L: %s %ld", which, at);
+      c = good, c.goal.ref_stride = 4;
+      CHECK(!ok(c) && named("ref_stride", 4), "loop stride: %s %ld", which, at);
+      c = good, c.goal.ref_phase = nullptr;
+      CHECK(ok(c), "no phases refused: %s", which);
+      c = good, c.goal.ref_phase = ph_bad;
+      CHECK(!ok(c) && named("ref_phase", 2), "loop phase: %s %ld", which, at);
+      std::vector<int32_t> off_bad = off4;
+      off_bad[3] = -4;
+      c = good, c.goal.ref_offset = off_bad.data();
+      CHECK(!ok(c) && named("ref_offset", 3), "negative offset: %s %ld", which, at);
+      // the scans stop at G and num_steps: a bad entry beyond them belongs to nobody
+      c = good, c.G = 2, c.goal.ref_phase = ph_bad;
+      CHECK(ok(c), "the phase scan reads past G: %s %ld", which, at);
+      c = good, c.num_steps = 3, c.o.n_actual = 1, c.goal.ref_offset = off_bad.data();
+      CHECK(ok(c), "the offset scan reads past num_steps: %s %ld", which, at);
+      c = good, c.G = 0, c.goal.ref_phase = ph_bad;
+      CHECK(ok(c), "no groups reads no phases (loop): %s %ld", which, at);
+    }
+  }
+  // the session reads neither sim_dt nor n_actual, has no steps and needs no start states
+  {
+    SampledCall c = loop_call(SampledKind::tracking);
+    c.kind = SampledKind::session;
+    c.o.sim_dt = 0.0;
+    c.o.n_actual = 3;
+    c.xstart = c.f_actual = c.hist_out = nullptr;
+    c.goal.ref_offset = nullptr;
+    CHECK(ok(c), "session: %s %ld", which, at);
+  }
+
+  // the refusal texts: the fragment of every `which` that callers and tests match
+  const auto text = [&](const char* w, long a) { return sampled_refusal("who", w, a, 12); };
+  const auto has = [&](const std::string& msg, const char* frag) { return msg.find(frag) != std::string::npos; };
+  CHECK(has(text("qp_mode", I7M_QP_BOX), "who: ") && has(text("qp_mode", I7M_QP_BOX), "I7M_QP_BOX"), "qp_mode text");
+  CHECK(has(text("H", 3), "H = 3"), "H text");
+  CHECK(has(text("G", 16), "G x H = 16") && has(text("G", 16), "max_batch=12"), "G text");
+  CHECK(has(text("L", 0), "L = 0"), "L text");
+  CHECK(has(text("ref_stride", 4), "ref_stride = 4"), "ref_stride text");
+  CHECK(has(text("ref_offset", 1), "ref_offset[1]"), "ref_offset entry text");
+  CHECK(has(text("ref_phase", 0), "ref_phase[0]") && has(text("ref_phase", 1), "ref_phase[1]"), "ref_phase text");
+  CHECK(has(text("sim_dt", 0), "sim_dt"), "sim_dt text");
+  CHECK(has(text("frame", 5), "frame"), "frame text");
+  CHECK(has(text("reset_what", 8), "RESET"), "reset_what text");
+  CHECK(has(text("n_actual", 3), "n_actual"), "n_actual text");
+  CHECK(has(text("n_endpoints", 0), "endpoint") && has(text("num_steps", -1), "num_steps"), "counts text");
+  CHECK(has(text("ref", 0), "null ref") && has(text("fhyp", 0), "null fhyp"), "null ref / fhyp text");
+  CHECK(has(text("ref_offset", -1), "null ref_offset"), "null ref_offset text");
+  CHECK(has(text("err_out", 0), "null err_out") && has(text("dist_out", 0), "null dist_out"), "history text");
+  for (const char* w : {"xstart", "endpoints", "f_actual"}) CHECK(has(text(w, 0), (std::string("null ") + w).c_str()), "null %s text", w);
+  CHECK(has(ctrl_step_refusal("who", "x_meas", 13), "x_meas[13]") && has(ctrl_step_refusal("who", "x_meas", -1), "null x_meas") &&
+            has(ctrl_step_refusal("who", "u_out", -1), "null u_out") && has(ctrl_step_refusal("who", "elapsed", 0), "elapsed") &&
+            has(ctrl_step_refusal("who", "ref_offset", -1), "ref_offset = -1"),
+        "step texts");
 
   // i7m_ctrl_step's
   std::vector<double> x(36, 0.25);

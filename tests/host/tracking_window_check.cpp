@@ -1,5 +1,6 @@
 // Host check of the tracking goal source's plan (indy7_mpc_amd/csrc/i7m_plan.h): the window-index
-// clamp track_index that the kernel and the host's initial window share, the schedule validation,
+// clamp track_index that the kernel and the host's initial window share, the schedule validation
+// (sampled_call_ok's scans of the phases and the offsets),
 // and the workspace request of i7m_mpc_run_tracking against hand-computed bytes, with the endpoint
 // request (i7m_mpc_run_sampled) unchanged.
 #include <cstdio>
@@ -46,15 +47,33 @@ int main() {
 
   // the schedule
   const char* which = "";
-  int at = -1;
+  long at = -1;
   const int32_t ph_ok[3] = {0, 17, 50}, ph_bad[3] = {0, -1, 50}, off_ok[4] = {0, 0, 1, 2}, off_bad[4] = {1, 2, 3, -4};
-  CHECK(track_schedule_ok(ph_ok, 3, off_ok, 4, &which, &at), "a valid schedule is refused");
-  CHECK(track_schedule_ok(nullptr, 3, off_ok, 4, &which, &at), "no phases is refused");
-  CHECK(track_schedule_ok(nullptr, 3, nullptr, 0, &which, &at), "no steps reads no offsets");
-  CHECK(!track_schedule_ok(ph_bad, 3, off_ok, 4, &which, &at) && std::string(which) == "ref_phase" && at == 1,
-        "negative phase: %s[%d]", which, at);
-  CHECK(!track_schedule_ok(ph_ok, 3, off_bad, 4, &which, &at) && std::string(which) == "ref_offset" && at == 3,
-        "negative offset: %s[%d]", which, at);
+  const double some[1] = {0};
+  const auto schedule_ok = [&](const int32_t* ref_phase, int G, const int32_t* ref_offset, int num_steps) {
+    SampledCall c;
+    c.kind = SampledKind::tracking;
+    c.max_batch = G;
+    c.dt = c.o.sim_dt = 0.01;
+    c.G = G;
+    c.H = 1;
+    c.num_steps = num_steps;
+    c.o.frame = I7M_WRENCH_WORLD;
+    c.o.n_actual = 1;
+    c.goal.ref = c.xstart = c.fhyp = c.f_actual = c.hist_out = some;
+    c.goal.L = 1;
+    c.goal.ref_stride = 3;
+    c.goal.ref_phase = ref_phase;
+    c.goal.ref_offset = ref_offset;
+    return sampled_call_ok(c, &which, &at);
+  };
+  CHECK(schedule_ok(ph_ok, 3, off_ok, 4), "a valid schedule is refused");
+  CHECK(schedule_ok(nullptr, 3, off_ok, 4), "no phases is refused");
+  CHECK(schedule_ok(nullptr, 3, nullptr, 0), "no steps reads no offsets");
+  CHECK(!schedule_ok(ph_bad, 3, off_ok, 4) && std::string(which) == "ref_phase" && at == 1,
+        "negative phase: %s[%ld]", which, at);
+  CHECK(!schedule_ok(ph_ok, 3, off_bad, 4) && std::string(which) == "ref_offset" && at == 3,
+        "negative offset: %s[%ld]", which, at);
 
   // the workspace of a tracking request, (G, H, N, steps) = (3, 4, 8, 6), L = 300, stride 6, phases,
   // noise, one actual wrench: by hand

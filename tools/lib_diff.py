@@ -5,9 +5,13 @@
 
 dump: one config-3 solve (B = 4096, N = 32, bench.py's draws), one config-4 solve (B = 256,
 N = 64, box rows), the notebook's 500-step closed loop (B = 1, N = 32), and the ADMM mode: config
-3, N = 64, odd batches, adaptive rho, the closing tests after max_iter, each streaming kernel forced.
-cmp: per output, how many problems differ at all, the largest relative difference, and for the
-closed loop the first step at which the goal distances differ.
+3, N = 64, odd batches, adaptive rho, the closing tests after max_iter, each streaming kernel forced;
+and the sampled-wrench family at (G, H, N) = (2, 4, 8), 3 steps, direct and ADMM: mpc_run_sampled with
+noise, mpc_run_tracking with phases and noise, a controller session in both x0 forms with noise and
+its ctrl_end (every array of the returned dicts, keys fam_*).
+cmp: per output, how many problems differ at all, the largest relative difference, for the
+closed loop the first step at which the goal distances differ, and per key of the family how many
+entries differ.
 """
 import json
 import os
@@ -79,8 +83,50 @@ def dump(path):
         out[key + "_state"] = np.concatenate(state[:4] + (state[4][:, None], rho[:, None]), axis=1)
         out[key + "_stats"] = np.concatenate([its, stat], axis=1)
         h.close()
+    out.update(family(_lib, m, ends))
     out["ver"] = np.array(_lib.version())
     np.savez(path, **out)
+
+
+def family(_lib, m, ends):
+    """The sampled-wrench entry points on fixed inputs: {fam_<mode>_<call>_<key>: array}."""
+    from indy7_mpc_amd.utils import figure8
+    G, H, N, steps = 2, 4, 8, 3
+    rng = np.random.default_rng(61)
+    xs = np.concatenate([rng.uniform(-1, 1, (G, 6)), rng.uniform(-0.5, 0.5, (G, 6))], axis=1)
+    fhyp = np.zeros((G, H, 6))
+    fhyp[:, :, :3] = rng.normal(0, 10.0, (G, H, 3))
+    fhyp[:, 0] = 0.0
+    fact, fhyp = fhyp[np.arange(G), (np.arange(G) + 1) % H].copy(), fhyp.reshape(G * H, 6)
+    noise = rng.normal(0, 2.0, (steps, G * H, 3))
+    ref = figure8(0.5, 0.55, [0, 0.4, 0.45], period=1.0, dt=0.01, cycles=3).reshape(-1, 6)
+    kw = dict(keep_best=True, decay=0.97)
+    out = {}
+    for mode, qp in (("direct", _lib.QP_DIRECT), ("admm", _lib.QP_ADMM)):
+        def handle():
+            return _lib.Handle(m, N=N, max_batch=G * H, qp_mode=qp)
+        calls = {}
+        h = handle()
+        calls["sampled"] = h.mpc_run_sampled(xs, ends, steps, fhyp, fact, noise=noise, sim_dt=0.01, **kw)
+        h.close()
+        h = handle()
+        calls["tracking"] = h.mpc_run_tracking(xs, ref, [1, 2, 4], fhyp, fact, ref_phase=[0, 17], noise=noise, sim_dt=0.01, **kw)
+        h.close()
+        for form, x0 in (("x0", xs), ("null", None)):
+            h = handle()
+            r = {"u0": h.ctrl_begin(ref, fhyp, x0=x0, groups=G, ref_phase=[0, 17], **kw)}
+            x = xs.copy()
+            for i, (el, off) in enumerate(((0.01, 1), (0.008, 1), (0.012, 3))):
+                x[:, :6] += el * x[:, 6:]  # any finite measurement serves: both builds get the same
+                for k, v in h.ctrl_step(x, el, off, noise=noise[i]).items():
+                    r[f"step{i}_{k}"] = v
+            r.update(h.ctrl_end())
+            h.close()
+            calls["ctrl_" + form] = r
+        for call, r in calls.items():
+            for k, v in r.items():
+                out[f"fam_{mode}_{call}_{k}"] = np.asarray(v)
+    return out
 
 
 def cmp(a, b):
@@ -100,6 +146,19 @@ def cmp(a, b):
         x, y = A[k], B[k]
         nz = np.nonzero((x != y) & ~(np.isnan(x) & np.isnan(y)))[0]
         print(f"{k}: first differing step {nz[0] if len(nz) else None}; max |diff| {np.nanmax(np.abs(x - y)):.3e}")
+    fam = sorted(k for k in set(A.files) | set(B.files) if k.startswith("fam_"))
+    total = 0
+    for k in fam:
+        if k not in A.files or k not in B.files:
+            print(f"{k}: only in {'A' if k in A.files else 'B'}")
+            total += 1
+            continue
+        x, y = A[k], B[k]
+        n = x.size if x.shape != y.shape else int(((x != y) & ~((x != x) & (y != y))).sum())
+        total += n
+        print(f"{k}: {n} of {x.size} entries differ")
+    if fam:
+        print(f"family: {len(fam)} keys, {total} differing entries in all")
 
 
 if __name__ == "__main__":
