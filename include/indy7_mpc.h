@@ -34,7 +34,13 @@
  *   i7m_rk4                    utils.rk4 (plant)              src/utils.py:3-18
  *   i7m_set_external_wrench    batch_sqp.set_external_wrench_batch  gato_controller.py:129
  *   i7m_mpc_run                MPC_OSQP.run_mpc over B instances     src/osqp_mpc.py:14-72
- *                              (batch axis of src/gato_mpc_batch.py:76-217)
+ *                              (one 0.01 s plant step per solve; the batch axis is that of
+ *                               src/gato_mpc_batch.py:84-100, the loop is not)
+ *   i7m_mpc_run_multirate      MPC_GATO_Batch.run_mpc over B instances   src/gato_mpc_batch.py:76-217
+ *                              (control_from = I7M_CONTROL_NEW), and
+ *                              MPC_GATO.run_mpc over B instances         src/gato_mpc.py:53-150
+ *                              (sim_dt 0.02, goal_radius 1e-2, control_from = I7M_CONTROL_PREV)
+ *   i7m_multirate_substeps     the inner while-loop of both, counted     src/gato_mpc_batch.py:171-199
  *   i7m_mpc_run_sampled        MPC_GATO_Batch_Sample.run_mpc over G controllers of H wrench
  *                              hypotheses       src/gato_mpc_batch_sample.py:106-300
  *                              (find_best_idx / resample_f_ext_batch, gato_controller.py:109-129)
@@ -83,7 +89,8 @@ extern "C" {
 #define I7M_MAX_N 64
 
 /* ABI revision, returned by i7m_abi_version(); bumped whenever an existing signature, struct
- * layout, field meaning or enum count changes.  8: i7m_ctrl_begin / i7m_ctrl_step / i7m_ctrl_end
+ * layout, field meaning or enum count changes.  9: i7m_multirate_opts_default /
+ * i7m_multirate_substeps / i7m_mpc_run_multirate (appended; nothing existing changed).  8: i7m_ctrl_begin / i7m_ctrl_step / i7m_ctrl_end
  * (appended; nothing existing changed).  7: i7m_mpc_run_tracking (appended; nothing
  * existing changed) (0.7 builds).  6: i7m_get_admm_status has the value 2 ("solved
  * inaccurate") and, after admm_max_iter, runs OSQP's closing tests (0.6 builds).  5: i7m_get_admm_status and i7m_get_admm_dual
@@ -96,7 +103,7 @@ extern "C" {
  * 2: i7m_aba / i7m_rk4 take a wrench `frame` before their outputs and i7m_set_external_wrench a
  * trailing `frame` (0.2 builds); 1 had neither.  A caller built against another revision must not
  * call through this library: compare first. */
-#define I7M_ABI_VERSION 8
+#define I7M_ABI_VERSION 9
 
 #define I7M_OK 0
 #define I7M_EINVAL -1   /* bad argument (size, null pointer, unsupported N) */
@@ -311,14 +318,78 @@ int i7m_rk4(i7m_handle* h, int32_t Bq, const double* q, const double* v, const d
  * (src/osqp_mpc.py:14-72) per instance — goal = endpoints[0] tiled, XU = 0, an initial solve,
  * then per step: goal distance of xcur (cyclic switch below 0.1, the instance stops above 1.1),
  * xu_new = SQP solve, the rk4 plant over 0.01 s with the PREVIOUS trajectory's controls, the
- * warm-start shift and the first / last state pins — all batched, state resident in HBM; the
- * batch-axis analogue of src/gato_mpc_batch.py:76-217.  xstart (B, 12), endpoints (E, 3);
+ * warm-start shift and the first / last state pins — all batched, state resident in HBM (the
+ * loop of src/gato_mpc_batch.py:76-217 itself is i7m_mpc_run_multirate).  xstart (B, 12), endpoints (E, 3);
  * dist_out (num_steps, B) goal distances (NaN once an instance has stopped); q_out
  * (num_steps, B, 6) q after each step's plant, xcur_out (B, 12), xu_out (B, T) the final state
  * and warm start: each may be NULL but dist_out.  Synchronous.  I7M_EINVAL if the handle has an
  * external wrench set (MPC_OSQP's loop has none, src/osqp_mpc.py:56). */
 int i7m_mpc_run(i7m_handle* h, int32_t B, const double* xstart, const double* endpoints, int32_t n_endpoints,
                 int32_t num_steps, double* dist_out, double* q_out, double* xcur_out, double* xu_out);
+
+/* Options of i7m_mpc_run_multirate; fill with i7m_multirate_opts_default, then change fields. */
+#define I7M_CONTROL_NEW 0   /* the plant is driven by this step's solve: MPC_GATO_Batch, src/gato_mpc_batch.py:185 */
+#define I7M_CONTROL_PREV 1  /* by the warm start the solve started from: MPC_GATO, src/gato_mpc.py:126 */
+typedef struct i7m_multirate_opts {
+  double sim_dt;        /* plant time per solve, finite and > 0, not bounded by dt; default 0.001
+                           (src/gato_mpc_batch.py:76; MPC_GATO hard-codes 0.02, src/gato_mpc.py:76) */
+  double goal_radius;   /* default 0.1 (src/gato_mpc_batch.py:158; MPC_GATO: 1e-2, src/gato_mpc.py:106) */
+  int32_t control_from; /* I7M_CONTROL_*; default NEW */
+  int32_t reset_what;   /* I7M_QP_ADMM: I7M_ADMM_RESET_* bits applied to every instance before each
+                           step's solve; default ALL (solver.reset(), :116); 0 carries the OSQP state */
+} i7m_multirate_opts;
+int i7m_multirate_opts_default(i7m_multirate_opts* opts);
+
+/* Pure host: the total number of plant sub-steps of a run of num_steps MPC steps, to size
+ * xpath_out; I7M_EINVAL with i7m_mpc_run_multirate's refusals of sim_dt. */
+int i7m_multirate_substeps(double dt, double sim_dt, int32_t N, int32_t num_steps, int32_t* n_sub);
+
+/* Multi-rate closed loop of B independent instances on the device: MPC_GATO_Batch.run_mpc
+ * (src/gato_mpc_batch.py:76-217) and, with other options, MPC_GATO.run_mpc (src/gato_mpc.py:53-150).
+ * The plant advances opts->sim_dt per solve against the handle's knot grid dt: ten solves per knot
+ * with 0.001 / 0.01, two knots per solve with 0.02 / 0.01.
+ *   init    goal = endpoints[0] tiled; XU = 0 but XU[:12] = xstart; the solver state afresh;
+ *           XU = sqp(XU) (:84-100)
+ *   step i, every instance still running, in the reference's order:
+ *     reset    I7M_QP_ADMM: opts->reset_what on every instance (:116)
+ *     solve    xu_new = sqp(xcur, goal, XU), against the goal before any switch of this step (:121)
+ *     distance d = |eepos(xcur q) - goal|, dist_out[i, b] = d; u_out[i, b] = XU[12:18], the warm
+ *              start's first control before this step's update (the reference's control_inputs, :153)
+ *     goal     d < goal_radius: the next endpoint, goal rows re-tiled (not cyclic, :158-165); at the
+ *              last endpoint the instance stops here, before the plant (:166-168): q_out[i, b] and
+ *              this step's xpath slots are NaN.  There is no stop at 1.1.
+ *     plant    the step's sim_dt is split where it crosses a knot boundary: a time accumulator,
+ *              carried over all steps, holds the position inside the current knot; each sub-step
+ *              ts = min(remaining, dt - accumulated) is one rk4 step without a wrench, and a knot
+ *              completes when |accumulated - dt| < 1e-10 (:171-199).  The split depends on dt,
+ *              sim_dt and i alone and is computed on the host in the reference's double arithmetic;
+ *              its float residues are kept (dt 0.01, sim_dt 0.001: step 9 is [0.001, 8.67e-19], the
+ *              second a real rk4 call and a real xpath entry).  Every sub-step is driven by knot
+ *              0's control, u = xu_new[12:18] (I7M_CONTROL_NEW, :185) or XU[12:18] (I7M_CONTROL_PREV,
+ *              src/gato_mpc.py:126): the reference's current_interval is always 0, because the
+ *              accumulator is reset at every boundary.  xpath_out[s, b] = q after sub-step s (the
+ *              reference's self.xpath), q_out[i, b] = q after the last one.
+ *     shift    with s > 0 knots completed XU[:T - 18 s] = xu_new[18 s:], the tail keeping its old
+ *              values (:202-203); with s = 0 XU stays the OLDER trajectory: xu_new drove the plant
+ *              only.  Then XU[:12] = xcur, XU[-12:] = [1]*6 + [0]*6 (:206-207).
+ * An instance that stopped at step i has dist_out[i] and u_out[i] recorded and q_out[i], its xpath
+ * slots of step i NaN; from step i + 1 on all four are NaN.
+ * Deliberately not reproduced: src/gato_mpc_batch.py:213 with no knot completed, whose slice
+ * `:-(0) or len(XU_batch)` ends at batch_size and overwrites the first batch_size warm-start
+ * entries of every row with row 0's.
+ * xstart (B, 12), endpoints (E, 3); opts NULL = the defaults.  Outputs: dist_out (num_steps, B)
+ * required; q_out and u_out (num_steps, B, 6), xpath_out (n_sub, B, 6) with n_sub from
+ * i7m_multirate_substeps(dt, sim_dt, N, num_steps), xcur_out (B, 12), xu_out (B, T): each may be
+ * NULL.  num_steps = 0 reduces to the initial solve.  Synchronous.  A large I7M_QP_ADMM batch runs
+ * as its two staggered ranges, as i7m_mpc_run's.  I7M_QP_DIRECT and I7M_QP_ADMM; I7M_EINVAL with a
+ * message naming the argument, before any device work: I7M_QP_BOX; an external wrench set on the
+ * handle (neither driver's plant has one); sim_dt not finite or not positive; a step that completes
+ * more than N - 1 knots; a step of more than 66 sub-steps (sim_dt > 64 dt); a bad control_from or
+ * reset_what; null xstart, endpoints or dist_out. */
+int i7m_mpc_run_multirate(i7m_handle* h, int32_t B, const double* xstart, const double* endpoints, int32_t n_endpoints,
+                          int32_t num_steps, const i7m_multirate_opts* opts, double* dist_out /* (steps,B) required */,
+                          double* q_out /* (steps,B,6) */, double* u_out /* (steps,B,6) */,
+                          double* xpath_out /* (n_sub,B,6) */, double* xcur_out, double* xu_out);
 
 /* Options of i7m_mpc_run_sampled; fill with i7m_sampled_opts_default, then change fields. */
 typedef struct i7m_sampled_opts {
@@ -466,7 +537,7 @@ int i7m_mpc_run_tracking(i7m_handle* h, int32_t G, int32_t H, const double* xsta
  * session as it was.
  * While a session is open the entry points that would overwrite its rows, goals, wrenches or
  * solver state are refused ("controller session open"): i7m_solve, i7m_solve_device, i7m_qp,
- * i7m_qp_value, i7m_linearize, i7m_merit, i7m_linesearch, the three i7m_mpc_run*,
+ * i7m_qp_value, i7m_linearize, i7m_merit, i7m_linesearch, the four i7m_mpc_run*,
  * i7m_set_external_wrench, i7m_reset, i7m_admm_reset, i7m_set_stream.  The getters, the timing
  * calls, i7m_synchronize and the query hooks (i7m_eepos, i7m_aba, i7m_aba_derivatives, i7m_rk4:
  * they use scratch the session does not rely on between steps) stay available. */

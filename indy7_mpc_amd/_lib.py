@@ -20,7 +20,7 @@ import numpy as np
 LIB_DIR = os.path.join(os.path.dirname(os.path.abspath(__file__)), "lib")
 LIB_PATH = os.environ.get("I7M_LIB", os.path.join(LIB_DIR, "libindy7mpc.so"))  # I7M_LIB: A/B builds
 
-ABI_VERSION = 8  # I7M_ABI_VERSION of include/indy7_mpc.h this binding's SIGNATURES follow
+ABI_VERSION = 9  # I7M_ABI_VERSION of include/indy7_mpc.h this binding's SIGNATURES follow
 NJ, NX, NU = 6, 12, 6
 MAX_SQP = 8
 MAX_N = 64
@@ -96,6 +96,9 @@ ADMM_DEFAULTS = dict(rho=0.1, sigma=1e-6, alpha=1.6, eps_abs=1e-3, eps_rel=1e-3,
                      scaling=10, check_dualgap=True, adaptive_rho_interval=0, adaptive_rho_tolerance=5.0)
 PIPE_AUTO, PIPE_SPLIT, PIPE_FUSED, PIPE_FUSED_ITER = 0, 1, 2, 3
 WRENCH_LOCAL, WRENCH_WORLD = 0, 1
+CONTROL_NEW, CONTROL_PREV = 0, 1  # i7m_multirate_opts.control_from
+_CONTROLS = {"new": CONTROL_NEW, "prev": CONTROL_PREV, CONTROL_NEW: CONTROL_NEW, CONTROL_PREV: CONTROL_PREV}
+MULTIRATE_MAX_SUB = 66  # i7m_plan.h
 _FRAMES = {"local": WRENCH_LOCAL, "world": WRENCH_WORLD, WRENCH_LOCAL: WRENCH_LOCAL, WRENCH_WORLD: WRENCH_WORLD}
 BOX_Q, BOX_V, BOX_U = 1, 2, 4
 
@@ -125,6 +128,15 @@ class i7m_sampled_opts(C.Structure):
         ("reset_what", C.c_int32),
         ("keep_best", C.c_int32),
         ("n_actual", C.c_int32),
+    ]
+
+
+class i7m_multirate_opts(C.Structure):
+    _fields_ = [
+        ("sim_dt", C.c_double),
+        ("goal_radius", C.c_double),
+        ("control_from", C.c_int32),
+        ("reset_what", C.c_int32),
     ]
 
 
@@ -163,6 +175,10 @@ SIGNATURES = [
     ("i7m_aba_derivatives", C.c_int, [_H, C.c_int32, _DP, _DP, _DP, _DP, _DP, _DP, _DP]),
     ("i7m_rk4", C.c_int, [_H, C.c_int32, _DP, _DP, _DP, C.c_double, _DP, C.c_int32, _DP, _DP]),
     ("i7m_mpc_run", C.c_int, [_H, C.c_int32, _DP, _DP, C.c_int32, C.c_int32, _DP, _DP, _DP, _DP]),
+    ("i7m_multirate_opts_default", C.c_int, [C.POINTER(i7m_multirate_opts)]),
+    ("i7m_multirate_substeps", C.c_int, [C.c_double, C.c_double, C.c_int32, C.c_int32, _IP32]),
+    ("i7m_mpc_run_multirate", C.c_int, [_H, C.c_int32, _DP, _DP, C.c_int32, C.c_int32, C.POINTER(i7m_multirate_opts),
+                                        _DP, _DP, _DP, _DP, _DP, _DP]),
     ("i7m_sampled_opts_default", C.c_int, [C.POINTER(i7m_sampled_opts)]),
     ("i7m_mpc_run_sampled", C.c_int, [_H, C.c_int32, C.c_int32, _DP, _DP, C.c_int32, C.c_int32, _DP, _DP, _DP,
                                       C.POINTER(i7m_sampled_opts), _DP, _IP32, _DP, _DP, _DP, _DP, _DP]),
@@ -240,6 +256,39 @@ def _ptr(a):
 def _iptr(a):
     """int32 array, or None"""
     return None if a is None else a.ctypes.data_as(_IP32)
+
+
+def multirate_schedule(dt, sim_dt, num_steps, N=None):
+    """The plant's sub-steps of a multi-rate run (i7m_plan.h multirate_schedule, the same double
+    arithmetic in the same order: the reference's inner while-loop, src/gato_mpc_batch.py:171-199):
+    (sub_start (num_steps + 1,) int32, sub_dt (S,), shift (num_steps,) int32).  Step i owns sub-steps
+    [sub_start[i], sub_start[i + 1]) and completes shift[i] knots.  The float residues are kept
+    (dt 0.01, sim_dt 0.001: step 9 is [0.001, 8.67e-19]).  ValueError for what the library refuses:
+    sim_dt not finite or not positive, more than MULTIRATE_MAX_SUB sub-steps in a step and, with N
+    given, a step that completes more than N - 1 knots."""
+    dt, sim_dt = float(dt), float(sim_dt)
+    if not np.isfinite(sim_dt) or not sim_dt > 0.0:
+        raise ValueError("sim_dt must be finite and > 0")
+    sub_start, sub_dt, shift = [0], [], []
+    acc = 0.0  # carried over all steps
+    for i in range(int(num_steps)):
+        rem, sh, n = sim_dt, 0, 0
+        while rem > 0.0:
+            n += 1
+            if n > MULTIRATE_MAX_SUB:
+                raise ValueError(f"sim_dt = {sim_dt} needs more than {MULTIRATE_MAX_SUB} plant sub-steps in step {i}")
+            ts = min(rem, dt - acc)
+            acc += ts
+            rem -= ts
+            sub_dt.append(ts)
+            if abs(acc - dt) < 1e-10:
+                sh += 1
+                acc = 0.0
+        if N is not None and sh > N - 1:
+            raise ValueError(f"sim_dt = {sim_dt} completes more than N - 1 = {N - 1} knots in step {i}")
+        shift.append(sh)
+        sub_start.append(len(sub_dt))
+    return np.array(sub_start, dtype=np.int32), np.array(sub_dt, dtype=np.float64), np.array(shift, dtype=np.int32)
 
 
 class Handle:
@@ -463,6 +512,35 @@ class Handle:
         _check(self._lib.i7m_mpc_run(self._h, B, _ptr(xs), _ptr(ep), ep.shape[0], int(num_steps), _ptr(d), _ptr(q),
                                      _ptr(xc), _ptr(xu)))
         return d, q, xc, xu
+
+    def mpc_run_multirate(self, xstart, endpoints, num_steps, sim_dt=0.001, goal_radius=0.1, control_from="new",
+                          reset_what=ADMM_RESET_ALL):
+        """Multi-rate closed loop of B instances on the device (i7m_mpc_run_multirate): the plant
+        advances sim_dt per solve against the knot grid dt, split at knot boundaries, the warm start
+        shifted by the knots each step completes.  control_from "new" (MPC_GATO_Batch) or "prev"
+        (MPC_GATO).  Returns a dict: dist (num_steps, B), q and u (num_steps, B, 6), xpath (S, B, 6)
+        one q per plant sub-step, xcur (B, 12), xu (B, T), and the schedule the library ran, from
+        i7m_multirate_substeps and the same arithmetic here: sub_start (num_steps + 1,), shift
+        (num_steps,) (step i wrote xpath[sub_start[i]:sub_start[i + 1]]).  NaN from an instance's stop on."""
+        xs = _f64(xstart).reshape(-1, NX)
+        ep = _f64(endpoints).reshape(-1, 3)
+        B, num_steps = xs.shape[0], int(num_steps)
+        o = i7m_multirate_opts()
+        _check(self._lib.i7m_multirate_opts_default(C.byref(o)))
+        o.sim_dt, o.goal_radius = float(sim_dt), float(goal_radius)
+        o.control_from, o.reset_what = _CONTROLS[control_from], int(reset_what)
+        n_sub = C.c_int32(0)
+        _check(self._lib.i7m_multirate_substeps(self.cfg.dt, o.sim_dt, self.N, num_steps, C.byref(n_sub)))
+        sub_start, _, shift = multirate_schedule(self.cfg.dt, o.sim_dt, num_steps, self.N)
+        if sub_start[-1] != n_sub.value:
+            raise I7MError(f"the library plans {n_sub.value} sub-steps, this binding {sub_start[-1]}")
+        out = dict(dist=np.empty((num_steps, B)), q=np.empty((num_steps, B, NJ)), u=np.empty((num_steps, B, NU)),
+                   xpath=np.empty((n_sub.value, B, NJ)), xcur=np.empty((B, NX)), xu=np.empty((B, self.T)),
+                   sub_start=sub_start, shift=shift)
+        _check(self._lib.i7m_mpc_run_multirate(self._h, B, _ptr(xs), _ptr(ep), ep.shape[0], num_steps, C.byref(o),
+                                               _ptr(out["dist"]), _ptr(out["q"]), _ptr(out["u"]), _ptr(out["xpath"]),
+                                               _ptr(out["xcur"]), _ptr(out["xu"])))
+        return out
 
     # ---- the sampled-wrench family: what its three entry points parse the same way -------------
     @staticmethod

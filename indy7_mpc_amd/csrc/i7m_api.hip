@@ -26,6 +26,7 @@
 #include "i7m_mpc.h"
 #include "i7m_mpc_sampled.h"
 #include "i7m_ctrl.h"
+#include "i7m_mpc_multirate.h"
 #include "i7m_plan.h"
 
 // Source hash of the tree this library was built from (__graft_entry__.build passes it), so
@@ -57,6 +58,9 @@ hipError_t i7m_launch_sqp_fused(bool spec, int W, bool fext_world, int it, hipSt
                                 const double* xs, const double* goals, const double* fext, double* lin, double* cost,
                                 double* qpd, double* kbuf, double* sol, int* active, void* stats);
 hipError_t i7m_prepare_sqp_fused(int dev, int N);
+
+// i7m_mpc_multirate_tu.hip (k_mpc_multirate_step in a unit of its own); args: const MultirateArgs*
+hipError_t i7m_launch_multirate_step(int n, hipStream_t s, const void* model, const void* args);
 
 static_assert(sizeof(i7m_problem_stats) == sizeof(ProblemStats), "stats layout");
 static_assert(ADMM_RES_MAX_N == ARES_N, "i7m_plan.h: k_admm_iter_res's horizon");
@@ -1659,6 +1663,131 @@ int i7m_mpc_run(i7m_handle* h, int32_t B, const double* xstart, const double* en
   if (num_steps > 0) {
     if ((rc = copy_out(h, dist_out, d_dist, (size_t)num_steps * B))) return rc;
     if (q_out && (rc = copy_out(h, q_out, d_q, (size_t)num_steps * B * 6))) return rc;
+  }
+  if (xcur_out && (rc = copy_out(h, xcur_out, h->d_xs, (size_t)B * 12))) return rc;
+  if (xu_out && (rc = copy_out(h, xu_out, h->d_xu, (size_t)B * T))) return rc;
+  return i7m_synchronize(h);
+}
+
+int i7m_multirate_opts_default(i7m_multirate_opts* o) {
+  if (!o) return fail(I7M_EINVAL, "null opts");
+  o->sim_dt = 0.001;      // MPC_GATO_Batch.run_mpc's default, src/gato_mpc_batch.py:76
+  o->goal_radius = 0.1;   // :158
+  o->control_from = I7M_CONTROL_NEW;    // :185
+  o->reset_what = I7M_ADMM_RESET_ALL;  // solver.reset() before every solve, :116
+  return I7M_OK;
+}
+
+int i7m_multirate_substeps(double dt, double sim_dt, int32_t N, int32_t num_steps, int32_t* n_sub) {
+  const std::string who = "multirate_substeps";
+  if (!n_sub) return fail(I7M_EINVAL, who + ": null n_sub");
+  if (num_steps < 0) return fail(I7M_EINVAL, who + ": num_steps = " + std::to_string(num_steps) + ", need num_steps >= 0");
+  MultirateSchedule sch;
+  const char* which = "";
+  long at = 0;
+  if (!multirate_schedule(dt, sim_dt, N, num_steps, &sch, &which, &at))
+    return fail(I7M_EINVAL, multirate_refusal(who, which, at, sim_dt, N));
+  *n_sub = sch.total();
+  return I7M_OK;
+}
+
+int i7m_mpc_run_multirate(i7m_handle* h, int32_t B, const double* xstart, const double* endpoints, int32_t n_endpoints,
+                          int32_t num_steps, const i7m_multirate_opts* opts, double* dist_out, double* q_out,
+                          double* u_out, double* xpath_out, double* xcur_out, double* xu_out) {
+  const std::string who = "mpc_run_multirate";
+  int rc = check_batch(h, B, 3);
+  if (rc) return rc;
+  i7m_multirate_opts o;
+  (void)i7m_multirate_opts_default(&o);
+  if (opts) o = *opts;
+  if (h->cfg.qp_mode != I7M_QP_DIRECT && h->cfg.qp_mode != I7M_QP_ADMM)
+    return fail(I7M_EINVAL, who + ": I7M_QP_BOX is not supported (I7M_QP_DIRECT or I7M_QP_ADMM)");
+  if (n_endpoints < 1) return fail(I7M_EINVAL, who + ": n_endpoints = " + std::to_string(n_endpoints) + ", need >= 1 endpoint");
+  if (num_steps < 0) return fail(I7M_EINVAL, who + ": num_steps = " + std::to_string(num_steps) + ", need num_steps >= 0");
+  if (o.control_from != I7M_CONTROL_NEW && o.control_from != I7M_CONTROL_PREV)
+    return fail(I7M_EINVAL, who + ": control_from must be I7M_CONTROL_NEW or I7M_CONTROL_PREV");
+  if (o.reset_what & ~I7M_ADMM_RESET_ALL) return fail(I7M_EINVAL, who + ": reset_what has unknown I7M_ADMM_RESET_* bits");
+  if (!std::isfinite(o.goal_radius)) return fail(I7M_EINVAL, who + ": goal_radius must be finite");
+  if (!xstart) return fail(I7M_EINVAL, who + ": null xstart");
+  if (!endpoints) return fail(I7M_EINVAL, who + ": null endpoints");
+  if (!dist_out) return fail(I7M_EINVAL, who + ": null dist_out");
+  // neither driver's plant has an external wrench (src/gato_mpc_batch.py:188, src/gato_mpc.py:129
+  // call rk4 without f_ext): with one set the planner would use it and the plant would not
+  if (h->has_fext)
+    return fail(I7M_EINVAL, who + ": the handle has an external wrench set; the multi-rate closed loops have none "
+                                  "(clear it with i7m_set_external_wrench(h, 0, NULL, 0))");
+  const int N = (int)h->N;
+  MultirateSchedule sch;
+  const char* which = "";
+  long at = 0;
+  if (!multirate_schedule(h->cfg.dt, o.sim_dt, N, num_steps, &sch, &which, &at))
+    return fail(I7M_EINVAL, multirate_refusal(who, which, at, o.sim_dt, N));
+  if (B == 0) return I7M_OK;
+  HIPCHK(hipSetDevice(h->dev));
+  const size_t T = h->T;
+  const int n_sub = sch.total();
+  const bool admm = h->cfg.qp_mode == I7M_QP_ADMM;
+  size_t bytes[MULTIRATE_WS_COUNT];
+  multirate_ws_bytes(B, n_endpoints, num_steps, n_sub, bytes);
+  // host staging, declared first: alive until the workspace's final synchronize
+  const LoopStart start(h, B, B, endpoints);
+  const std::vector<double> rho0((size_t)B, h->cfg.admm_rho);
+  Workspace ws(h, bytes);
+  if (!ws.base) return fail(I7M_ENOMEM, who + ": device allocation failed");
+  double *d_ep = ws.at<double>(MRWS_EP), *d_dist = ws.at<double>(MRWS_DIST), *d_q = ws.at<double>(MRWS_Q),
+         *d_u = ws.at<double>(MRWS_U), *d_xp = ws.at<double>(MRWS_XPATH), *d_sub = ws.at<double>(MRWS_SUBDT),
+         *d_rho0 = ws.at<double>(MRWS_RHO0);
+  int *d_gi = ws.at<int>(MRWS_GI), *d_alive = ws.at<int>(MRWS_ALIVE);
+  // src/gato_mpc_batch.py:84-100: goal = endpoint 0 tiled, XU = [xstart, 0...], XU = sqp(xcur, goal, XU)
+  if ((rc = copy_in(h, h->d_xs, xstart, (size_t)B * 12))) return rc;
+  if ((rc = loop_start(h, start, endpoints, n_endpoints, d_ep, d_gi, d_alive))) return rc;
+  HIPCHK(hipMemcpy2DAsync(h->d_xu, T * 8, xstart, 12 * 8, 12 * 8, B, hipMemcpyHostToDevice, h->stream));
+  if ((rc = copy_in(h, d_rho0, rho0.data(), (size_t)B))) return rc;
+  if (n_sub > 0 && (rc = copy_in(h, d_sub, sch.sub_dt.data(), (size_t)n_sub))) return rc;
+  // the instances [lo, lo + n) through every MPC step on stream s, as i7m_mpc_run's ranges
+  rc = run_ranges(h, B, [&](long lo, int n, hipStream_t s, StaggerMark* mark) -> int {
+    double *xu = h->d_xu + lo * T, *out = h->d_out + lo * T, *xs = h->d_xs + lo * 12, *g = h->d_goal + lo * 3 * N;
+    // the solver state of these instances afresh, asynchronous on s (ADMM mode)
+    auto reset = [&](int what) {
+      return admm && what ? admm_reset_rows(h, lo, n, what, s, d_rho0 + lo, hipMemcpyDeviceToDevice) : I7M_OK;
+    };
+    MultirateArgs a{};
+    a.N = N;
+    a.n_endpoints = n_endpoints;
+    a.control_prev = o.control_from == I7M_CONTROL_PREV;
+    a.hist_stride = B;
+    a.radius = o.goal_radius;
+    a.xs = xs;
+    a.XU = xu;
+    a.xu_new = out;
+    a.goals = g;
+    a.endpoints = d_ep;
+    a.goal_idx = d_gi + lo;
+    a.alive = d_alive + lo;
+    int rc3;
+    if ((rc3 = reset(I7M_ADMM_RESET_ALL))) return rc3;
+    if ((rc3 = run_sqp(h, n, xu, xu, xs, g, 3, nullptr, lo, s, mark))) return rc3;
+    for (int i = 0; i < num_steps; ++i) {
+      if ((rc3 = reset(o.reset_what))) return rc3;
+      // xu_new = sqp(xcur, goal, XU) into the scratch buffer d_out (XU itself is read only)
+      if ((rc3 = run_sqp(h, n, xu, out, xs, g, 3, nullptr, lo, s))) return rc3;
+      a.n_sub = sch.sub_start[i + 1] - sch.sub_start[i];
+      a.shift = sch.shift[i];
+      a.sub_dt = d_sub + sch.sub_start[i];
+      a.dist_out = d_dist + (size_t)i * B + lo;
+      a.q_out = d_q + ((size_t)i * B + lo) * 6;
+      a.u_out = d_u + ((size_t)i * B + lo) * 6;
+      a.xpath_out = d_xp + ((size_t)sch.sub_start[i] * B + lo) * 6;
+      HIPCHK(i7m_launch_multirate_step(n, s, h->d_model, &a));
+    }
+    return I7M_OK;
+  });
+  if (rc) return rc;
+  if (num_steps > 0) {
+    if ((rc = copy_out(h, dist_out, d_dist, (size_t)num_steps * B))) return rc;
+    if (q_out && (rc = copy_out(h, q_out, d_q, (size_t)num_steps * B * 6))) return rc;
+    if (u_out && (rc = copy_out(h, u_out, d_u, (size_t)num_steps * B * 6))) return rc;
+    if (xpath_out && (rc = copy_out(h, xpath_out, d_xp, (size_t)n_sub * B * 6))) return rc;
   }
   if (xcur_out && (rc = copy_out(h, xcur_out, h->d_xs, (size_t)B * 12))) return rc;
   if (xu_out && (rc = copy_out(h, xu_out, h->d_xu, (size_t)B * T))) return rc;

@@ -10,6 +10,7 @@
 #include <cstdlib>
 #include <cstring>
 #include <string>
+#include <vector>
 
 #include "../../include/indy7_mpc.h"
 
@@ -289,6 +290,86 @@ inline void sampled_ws_bytes(int G, int H, int N, int num_steps, int n_endpoints
   bytes[SWS_RHO0] = 8 * B;
   bytes[SWS_BEST] = bytes[SWS_GI] = bytes[SWS_ALIVE] = 4 * (size_t)G;
   bytes[SWS_BH] = 4 * hist;
+}
+
+// ---- the multi-rate closed loop (i7m_mpc_run_multirate, i7m_mpc_multirate.h) ----------------------
+
+// The plant's sub-steps of every MPC step and the knots each step completes: the reference's inner
+// while-loop (src/gato_mpc_batch.py:171-199 = src/gato_mpc.py:118-140) run ahead of time.  It
+// depends on dt, sim_dt and the step index alone, never on a state, so the kernel gets a bounded
+// list and needs no open-ended loop.  Double arithmetic in the reference's order; the float
+// residues are its behaviour and are kept: with dt = 0.01, sim_dt = 0.001 the tenth step is
+// [0.001, 8.67e-19] (the accumulator reaches 0.01 - 8.67e-19 first), and that tiny sub-step is a
+// real rk4 call and a real xpath entry there too.
+// The reference's current_interval = int(time_accumulated / dt) (:179 / :125) is always 0: the
+// accumulator is reset whenever it reaches dt, so it stays below dt.  Every sub-step is driven by
+// knot 0's control and no knot index is carried.
+constexpr int MULTIRATE_MAX_SUB = 66;  // sub-steps of one MPC step: covers sim_dt <= 64 dt (64 whole knots, two partial)
+struct MultirateSchedule {
+  std::vector<int32_t> sub_start;  // (num_steps + 1) step i owns sub-steps [sub_start[i], sub_start[i + 1])
+  std::vector<double> sub_dt;      // (S) rk4 step lengths
+  std::vector<int32_t> shift;      // (num_steps) knots completed in step i: the warm-start shift
+  int total() const { return sub_start.empty() ? 0 : sub_start.back(); }
+};
+// False with *which = "sim_dt" (not finite or not positive), "shift" (step *at completes more than
+// N - 1 knots) or "substeps" (step *at needs more than MULTIRATE_MAX_SUB sub-steps; this bound also
+// ends the loop for any dt).  A refused schedule is left empty.
+inline bool multirate_schedule(double dt, double sim_dt, int N, int num_steps, MultirateSchedule* out,
+                               const char** which, long* at) {
+  const auto no = [&](const char* w, long a) {
+    *out = MultirateSchedule{};
+    *which = w;
+    *at = a;
+    return false;
+  };
+  *out = MultirateSchedule{};
+  if (!std::isfinite(sim_dt) || !(sim_dt > 0.0)) return no("sim_dt", 0);
+  out->sub_start.push_back(0);
+  double acc = 0.0;  // carried over all steps
+  for (int i = 0; i < num_steps; ++i) {
+    double rem = sim_dt;
+    int shift = 0, n = 0;
+    while (rem > 0.0) {
+      if (++n > MULTIRATE_MAX_SUB) return no("substeps", i);
+      const double ts = std::min(rem, dt - acc);
+      acc += ts;
+      rem -= ts;
+      out->sub_dt.push_back(ts);
+      if (std::fabs(acc - dt) < 1e-10) {
+        ++shift;
+        acc = 0.0;
+      }
+    }
+    if (shift > N - 1) return no("shift", i);
+    out->shift.push_back(shift);
+    out->sub_start.push_back((int32_t)out->sub_dt.size());
+  }
+  return true;
+}
+// The text of a refusal by multirate_schedule, for the entry point `who`.
+inline std::string multirate_refusal(const std::string& who, const std::string& which, long at, double sim_dt, int N) {
+  const std::string step = std::to_string(at), sd = std::to_string(sim_dt);
+  if (which == "shift")
+    return who + ": sim_dt = " + sd + " completes more than N - 1 = " + std::to_string(N - 1) + " knots in step " + step +
+           " (the warm-start shift would pass the horizon)";
+  if (which == "substeps")
+    return who + ": sim_dt = " + sd + " needs more than MULTIRATE_MAX_SUB = " + std::to_string(MULTIRATE_MAX_SUB) +
+           " plant sub-steps in step " + step;
+  return who + ": sim_dt must be finite and > 0";
+}
+// i7m_mpc_run_multirate's request: the endpoints; the distance, q and control histories (per step)
+// and the path (per sub-step); the sub-step lengths; the instances' initial rho (I7M_QP_ADMM
+// resets); goal index and alive flag per instance
+enum { MRWS_EP, MRWS_DIST, MRWS_Q, MRWS_U, MRWS_XPATH, MRWS_SUBDT, MRWS_RHO0, MRWS_GI, MRWS_ALIVE, MULTIRATE_WS_COUNT };
+inline void multirate_ws_bytes(int B, int n_endpoints, int num_steps, int n_sub, size_t bytes[MULTIRATE_WS_COUNT]) {
+  const size_t hist = history_rows(num_steps, B);
+  bytes[MRWS_EP] = 3 * 8 * (size_t)n_endpoints;
+  bytes[MRWS_DIST] = 8 * hist;
+  bytes[MRWS_Q] = bytes[MRWS_U] = 6 * 8 * hist;
+  bytes[MRWS_XPATH] = 6 * 8 * history_rows(n_sub, B);
+  bytes[MRWS_SUBDT] = 8 * (size_t)std::max(n_sub, 1);
+  bytes[MRWS_RHO0] = 8 * (size_t)B;
+  bytes[MRWS_GI] = bytes[MRWS_ALIVE] = 4 * (size_t)B;
 }
 
 // ---- the reference-tracking goal source of the sampled loop (i7m_mpc_run_tracking) ---------------
