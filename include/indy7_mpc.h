@@ -46,6 +46,10 @@
  *                              (find_best_idx / resample_f_ext_batch, gato_controller.py:109-129)
  *   i7m_mpc_run_tracking       GATO_Controller.joint_callback: that loop tracking a reference
  *                              trajectory                     gato_controller.py:201-250
+ *   i7m_mpc_run_sampled_multirate   that loop with the plant step split at knot boundaries
+ *                              (sim_dt not bounded by dt)     src/gato_mpc_batch_sample.py:163-193
+ *   i7m_mpc_run_tracking_multirate  MPC_GATO_Batch_Sample.run_mpc_fig8, the figure-8 tracking run
+ *                              under an unknown force         notebooks/gato_mpc_indy7_fig8.ipynb
  *   i7m_ctrl_begin / _step / _end   GATO_Controller.__init__ / joint_callback on a state measured
  *                              outside the device             gato_controller.py:174-185,201-250
  *
@@ -89,7 +93,9 @@ extern "C" {
 #define I7M_MAX_N 64
 
 /* ABI revision, returned by i7m_abi_version(); bumped whenever an existing signature, struct
- * layout, field meaning or enum count changes.  9: i7m_multirate_opts_default /
+ * layout, field meaning or enum count changes.  10: i7m_sampled_multirate_opts_default /
+ * i7m_mpc_run_sampled_multirate / i7m_mpc_run_tracking_multirate (appended; nothing existing
+ * changed).  9: i7m_multirate_opts_default /
  * i7m_multirate_substeps / i7m_mpc_run_multirate (appended; nothing existing changed).  8: i7m_ctrl_begin / i7m_ctrl_step / i7m_ctrl_end
  * (appended; nothing existing changed).  7: i7m_mpc_run_tracking (appended; nothing
  * existing changed) (0.7 builds).  6: i7m_get_admm_status has the value 2 ("solved
@@ -103,7 +109,7 @@ extern "C" {
  * 2: i7m_aba / i7m_rk4 take a wrench `frame` before their outputs and i7m_set_external_wrench a
  * trailing `frame` (0.2 builds); 1 had neither.  A caller built against another revision must not
  * call through this library: compare first. */
-#define I7M_ABI_VERSION 9
+#define I7M_ABI_VERSION 10
 
 #define I7M_OK 0
 #define I7M_EINVAL -1   /* bad argument (size, null pointer, unsupported N) */
@@ -480,6 +486,85 @@ int i7m_mpc_run_tracking(i7m_handle* h, int32_t G, int32_t H, const double* xsta
                          double* err_out, int32_t* best_out, double* q_out, double* ee_out, double* fbest_out,
                          double* xcur_out, double* xu_best_out, double* fhyp_out);
 
+/* Options of i7m_mpc_run_sampled_multirate / i7m_mpc_run_tracking_multirate; fill with
+ * i7m_sampled_multirate_opts_default, then change fields.  The first six are i7m_sampled_opts'
+ * fields with the same meanings and defaults, but for sim_dt's bound. */
+typedef struct i7m_sampled_multirate_opts {
+  double sim_dt;        /* plant time per solve, finite and > 0, NOT bounded by dt; default 0.001 */
+  double decay;         /* default 1 */
+  int32_t frame;        /* I7M_WRENCH_*; default WORLD */
+  int32_t reset_what;   /* I7M_ADMM_RESET_* bits before each step's solve; default ALL */
+  int32_t keep_best;    /* default 0 */
+  int32_t n_actual;     /* f_actual is (n_actual, G, 6): 1 or num_steps; default 1 */
+  int32_t shift_warm_start; /* 1: the rows' warm start is shifted by the knots a step completes
+                           (src/gato_mpc_batch.py:202-203's rule); default 0, as the reference's shift
+                           is commented out (src/gato_mpc_batch_sample.py:194-201) */
+  int32_t pad;          /* 0 */
+} i7m_sampled_multirate_opts;
+int i7m_sampled_multirate_opts_default(i7m_sampled_multirate_opts* opts);
+
+/* The sampled-wrench closed loops with a multi-rate plant: i7m_mpc_run_sampled and
+ * i7m_mpc_run_tracking where the plant advances opts->sim_dt per solve against the knot grid dt and
+ * a plant step is split where it crosses a knot boundary (src/gato_mpc_batch_sample.py:163-193;
+ * MPC_GATO_Batch_Sample.run_mpc_fig8 of notebooks/gato_mpc_indy7_fig8.ipynb, which steps 0.02 s per
+ * solve against 10 ms knots).  Init, groups and rows, H in {1, ..., 256}, reset, solve, the select
+ * and resample rule, the wrench left on the handle and the staggered ranges cut on a group boundary
+ * are i7m_mpc_run_sampled's / i7m_mpc_run_tracking's.  The schedule of sub-steps and completed knots
+ * is i7m_mpc_run_multirate's (computed on the host in the reference's double arithmetic, float
+ * residues kept: dt 0.01, sim_dt 0.001 gives step 9 the sub-steps [0.001, 8.67e-19]).
+ *   step i, every group still running:
+ *     plant    x_last = xcur[g], u_last = XU_best[g][12:18], u_out[i, g] = u_last.  The actual
+ *              wrench f_actual[i or 0][g], if world-frame, is converted to joint 6's frame ONCE, at
+ *              x_last's q, and held over all of the step's sub-steps (:151-161).  Each sub-step s
+ *              is one rk4 step of its length driven by u_last (the reference's current_knot is
+ *              always 0: the accumulator is reset at every boundary).  xpath_out[s, g] = q after
+ *              sub-step s, q_out[i, g] = q after the step's last.
+ *     spread   shift_warm_start = 0: every row of g gets xs = xcur[g], XU = [xcur[g], XU_best[g][12:]].
+ *              shift_warm_start = 1 and s = the knots this step completed > 0:
+ *              XU[e] = XU_best[g][e + 18 s] for 12 <= e < T - 18 s, the tail keeps XU_best[g][e]
+ *              (src/gato_mpc_batch.py:202-203).  No terminal pin.
+ *     goal     (endpoints) as i7m_mpc_run_sampled: radius 0.095, the next endpoint or the stop,
+ *              after the plant.  A group that stops at step i has dist / q / u / xpath of step i
+ *              recorded, best_out[i] = -1 and fbest_out[i] NaN; from step i + 1 on dist, q, u,
+ *              xpath and fbest are NaN and best is -1.
+ *     track    (reference) the window's offset is off_i = the knots completed by steps 0 .. i, the
+ *              notebook's eepos_offset; off_out[i] = off_i; err_out[i, g] = |eepos(xcur q) -
+ *              ref[min(ph_g + off_i, L - 1)]|, ee_out[i, g], and the rows' window at ph_g + off_i,
+ *              as i7m_mpc_run_tracking with ref_offset[i] = off_i.  A tracking group never stops.
+ *     reset, solve   as the existing loops
+ *     select   err_h = |rk4(x_last, u_last, sim_dt, wrench row h) - xcur[g]|_2: ONE rk4 step of the
+ *              whole sim_dt, not split (:284, the notebook's sim_forward(x_last, u_last, sim_dt)),
+ *              the hypothesis converted at x_last's q.  On a step with several sub-steps the true
+ *              hypothesis therefore scores small but not 0: the reference's behaviour.  On a step
+ *              with one sub-step plant and score are the same computation (the same conversion,
+ *              then the same rk4 code), and a hypothesis equal to the actual wrench scores as in
+ *              i7m_mpc_run_sampled.  The lowest index wins a tie, a NaN error never wins; then the
+ *              resample.
+ * Deliberately not reproduced: the actual force's random walk (:244-250; the caller supplies
+ * f_actual); the notebook's use of the world force as a local one (its actInv is commented out);
+ * np.random's global draw order.
+ * Outputs: dist_out / err_out (num_steps, G) required; best_out (num_steps, G) int32; q_out, u_out,
+ * fbest_out (num_steps, G, 6); xpath_out (n_sub, G, 6) with n_sub from i7m_multirate_substeps(dt,
+ * sim_dt, N, num_steps); ee_out (num_steps, G, 3); off_out (num_steps) int32; xcur_out (G, 12),
+ * xu_best_out (G, T), fhyp_out (G H, 6): each may be NULL.  num_steps = 0 reduces to the initial
+ * solve.  Synchronous.  I7M_EINVAL with the argument named, before any device work: everything
+ * i7m_mpc_run_sampled / i7m_mpc_run_tracking refuse except sim_dt > dt; sim_dt not finite or not
+ * positive; a step of more than 66 sub-steps; a step that completes more than N - 1 knots;
+ * shift_warm_start not 0 or 1; an open controller session; I7M_QP_BOX. */
+int i7m_mpc_run_sampled_multirate(i7m_handle* h, int32_t G, int32_t H, const double* xstart, const double* endpoints,
+                                  int32_t n_endpoints, int32_t num_steps, const double* fhyp, const double* f_actual,
+                                  const double* noise, const i7m_sampled_multirate_opts* opts,
+                                  double* dist_out /* (steps,G) required */, int32_t* best_out, double* q_out,
+                                  double* u_out /* (steps,G,6) */, double* xpath_out /* (n_sub,G,6) */,
+                                  double* fbest_out, double* xcur_out, double* xu_best_out, double* fhyp_out);
+int i7m_mpc_run_tracking_multirate(i7m_handle* h, int32_t G, int32_t H, const double* xstart, const double* ref,
+                                   int32_t L, int32_t ref_stride, const int32_t* ref_phase, int32_t num_steps,
+                                   const double* fhyp, const double* f_actual, const double* noise,
+                                   const i7m_sampled_multirate_opts* opts, double* err_out /* (steps,G) required */,
+                                   int32_t* best_out, double* q_out, double* u_out, double* xpath_out, double* ee_out,
+                                   int32_t* off_out /* (steps) */, double* fbest_out, double* xcur_out,
+                                   double* xu_best_out, double* fhyp_out);
+
 /* A controller session: GATO_Controller itself (gato_controller.py:144-250), one control step per
  * call on a state MEASURED by the caller (a robot, a simulator), where i7m_mpc_run_tracking owns
  * the plant.  G controllers of H hypotheses, group g owning rows [g H, (g + 1) H) as there; the
@@ -537,7 +622,7 @@ int i7m_mpc_run_tracking(i7m_handle* h, int32_t G, int32_t H, const double* xsta
  * session as it was.
  * While a session is open the entry points that would overwrite its rows, goals, wrenches or
  * solver state are refused ("controller session open"): i7m_solve, i7m_solve_device, i7m_qp,
- * i7m_qp_value, i7m_linearize, i7m_merit, i7m_linesearch, the four i7m_mpc_run*,
+ * i7m_qp_value, i7m_linearize, i7m_merit, i7m_linesearch, the six i7m_mpc_run*,
  * i7m_set_external_wrench, i7m_reset, i7m_admm_reset, i7m_set_stream.  The getters, the timing
  * calls, i7m_synchronize and the query hooks (i7m_eepos, i7m_aba, i7m_aba_derivatives, i7m_rk4:
  * they use scratch the session does not rely on between steps) stay available. */

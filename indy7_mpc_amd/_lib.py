@@ -20,7 +20,7 @@ import numpy as np
 LIB_DIR = os.path.join(os.path.dirname(os.path.abspath(__file__)), "lib")
 LIB_PATH = os.environ.get("I7M_LIB", os.path.join(LIB_DIR, "libindy7mpc.so"))  # I7M_LIB: A/B builds
 
-ABI_VERSION = 9  # I7M_ABI_VERSION of include/indy7_mpc.h this binding's SIGNATURES follow
+ABI_VERSION = 10  # I7M_ABI_VERSION of include/indy7_mpc.h this binding's SIGNATURES follow
 NJ, NX, NU = 6, 12, 6
 MAX_SQP = 8
 MAX_N = 64
@@ -131,6 +131,13 @@ class i7m_sampled_opts(C.Structure):
     ]
 
 
+class i7m_sampled_multirate_opts(C.Structure):
+    _fields_ = i7m_sampled_opts._fields_ + [
+        ("shift_warm_start", C.c_int32),
+        ("pad", C.c_int32),
+    ]
+
+
 class i7m_multirate_opts(C.Structure):
     _fields_ = [
         ("sim_dt", C.c_double),
@@ -185,6 +192,13 @@ SIGNATURES = [
     ("i7m_mpc_run_tracking", C.c_int, [_H, C.c_int32, C.c_int32, _DP, _DP, C.c_int32, C.c_int32, _IP32, _IP32, C.c_int32,
                                        _DP, _DP, _DP, C.POINTER(i7m_sampled_opts), _DP, _IP32, _DP, _DP, _DP, _DP, _DP,
                                        _DP]),
+    ("i7m_sampled_multirate_opts_default", C.c_int, [C.POINTER(i7m_sampled_multirate_opts)]),
+    ("i7m_mpc_run_sampled_multirate", C.c_int, [_H, C.c_int32, C.c_int32, _DP, _DP, C.c_int32, C.c_int32, _DP, _DP, _DP,
+                                                C.POINTER(i7m_sampled_multirate_opts), _DP, _IP32, _DP, _DP, _DP, _DP,
+                                                _DP, _DP, _DP]),
+    ("i7m_mpc_run_tracking_multirate", C.c_int, [_H, C.c_int32, C.c_int32, _DP, _DP, C.c_int32, C.c_int32, _IP32,
+                                                 C.c_int32, _DP, _DP, _DP, C.POINTER(i7m_sampled_multirate_opts), _DP,
+                                                 _IP32, _DP, _DP, _DP, _DP, _IP32, _DP, _DP, _DP, _DP]),
     ("i7m_ctrl_begin", C.c_int, [_H, C.c_int32, C.c_int32, _DP, _DP, C.c_int32, C.c_int32, _IP32, _DP,
                                  C.POINTER(i7m_sampled_opts), _DP]),
     ("i7m_ctrl_step", C.c_int, [_H, _DP, C.c_double, C.c_int32, _DP, _DP, _IP32, _DP, _DP, _DP]),
@@ -642,6 +656,76 @@ class Handle:
                                               _iptr(out["best"]), _ptr(out["q"]), _ptr(out["ee"]),
                                               _ptr(out["fbest"]), _ptr(out["xcur"]), _ptr(out["xu_best"]),
                                               _ptr(out["fhyp"])))
+        return out
+
+    def _multirate_opts(self, o, shift_warm_start):
+        """The multi-rate options struct from the family's (same fields first) and the shift flag."""
+        m = i7m_sampled_multirate_opts()
+        _check(self._lib.i7m_sampled_multirate_opts_default(C.byref(m)))
+        for f, _ in i7m_sampled_opts._fields_:
+            setattr(m, f, getattr(o, f))
+        m.shift_warm_start = int(shift_warm_start)
+        return m
+
+    def _multirate_plan(self, sim_dt, num_steps):
+        """(n_sub, sub_start, shift) of a run: the library's count (i7m_multirate_substeps, which
+        raises for what the library refuses) and this binding's schedule, which must agree."""
+        n_sub = C.c_int32(0)
+        _check(self._lib.i7m_multirate_substeps(self.cfg.dt, float(sim_dt), self.N, int(num_steps), C.byref(n_sub)))
+        sub_start, _, shift = multirate_schedule(self.cfg.dt, sim_dt, num_steps, self.N)
+        if sub_start[-1] != n_sub.value:
+            raise I7MError(f"the library plans {n_sub.value} sub-steps, this binding {sub_start[-1]}")
+        return n_sub.value, sub_start, shift
+
+    def mpc_run_sampled_multirate(self, xstart, endpoints, num_steps, fhyp, f_actual, noise=None, sim_dt=0.001,
+                                  frame="world", reset_what=ADMM_RESET_ALL, keep_best=False, decay=1.0,
+                                  shift_warm_start=0):
+        """mpc_run_sampled with a multi-rate plant (i7m_mpc_run_sampled_multirate): sim_dt is not
+        bounded by dt, a plant step is split at knot boundaries, the hypotheses are scored by one rk4
+        step of the whole sim_dt.  shift_warm_start=1 shifts the rows' warm start by the knots a step
+        completes.  Returns mpc_run_sampled's dict plus u (num_steps, G, 6) the control applied at
+        each step, xpath (n_sub, G, 6) one q per plant sub-step, and the schedule: sub_start
+        (num_steps + 1,), shift (num_steps,)."""
+        ep = _f64(endpoints).reshape(-1, 3)
+        num_steps = int(num_steps)
+        xs, G, fh, Hn, fa, nz, o = self._sampled_inputs(xstart, num_steps, fhyp, f_actual, noise, sim_dt, frame,
+                                                         reset_what, keep_best, decay)
+        m = self._multirate_opts(o, shift_warm_start)
+        n_sub, sub_start, shift = self._multirate_plan(sim_dt, num_steps)
+        out = dict(dist=np.empty((num_steps, G)), best=np.empty((num_steps, G), dtype=np.int32),
+                   q=np.empty((num_steps, G, NJ)), u=np.empty((num_steps, G, NU)), xpath=np.empty((n_sub, G, NJ)),
+                   fbest=np.empty((num_steps, G, 6)), xcur=np.empty((G, NX)), xu_best=np.empty((G, self.T)),
+                   fhyp=np.empty((G * Hn, 6)), sub_start=sub_start, shift=shift)
+        _check(self._lib.i7m_mpc_run_sampled_multirate(
+            self._h, G, Hn, _ptr(xs), _ptr(ep), ep.shape[0], num_steps, _ptr(fh), _ptr(fa), _ptr(nz), C.byref(m),
+            _ptr(out["dist"]), _iptr(out["best"]), _ptr(out["q"]), _ptr(out["u"]), _ptr(out["xpath"]),
+            _ptr(out["fbest"]), _ptr(out["xcur"]), _ptr(out["xu_best"]), _ptr(out["fhyp"])))
+        return out
+
+    def mpc_run_tracking_multirate(self, xstart, ref, num_steps, fhyp, f_actual, ref_phase=None, noise=None,
+                                   sim_dt=0.02, frame="world", reset_what=ADMM_RESET_ALL, keep_best=False, decay=1.0,
+                                   shift_warm_start=0):
+        """mpc_run_tracking with a multi-rate plant (i7m_mpc_run_tracking_multirate): the window's
+        offset at step i is the number of knots the plant has completed by then (the notebook's
+        eepos_offset), computed by the library.  Returns mpc_run_tracking's dict plus u, xpath, off
+        (num_steps,) int32 those offsets, sub_start and shift."""
+        rf = self._reference(ref)
+        num_steps = int(num_steps)
+        xs, G, fh, Hn, fa, nz, o = self._sampled_inputs(xstart, num_steps, fhyp, f_actual, noise, sim_dt, frame,
+                                                         reset_what, keep_best, decay)
+        rp = self._phases(ref_phase, G)
+        m = self._multirate_opts(o, shift_warm_start)
+        n_sub, sub_start, shift = self._multirate_plan(sim_dt, num_steps)
+        out = dict(err=np.empty((num_steps, G)), best=np.empty((num_steps, G), dtype=np.int32),
+                   q=np.empty((num_steps, G, NJ)), u=np.empty((num_steps, G, NU)), xpath=np.empty((n_sub, G, NJ)),
+                   ee=np.empty((num_steps, G, 3)), off=np.empty(num_steps, dtype=np.int32),
+                   fbest=np.empty((num_steps, G, 6)), xcur=np.empty((G, NX)), xu_best=np.empty((G, self.T)),
+                   fhyp=np.empty((G * Hn, 6)), sub_start=sub_start, shift=shift)
+        _check(self._lib.i7m_mpc_run_tracking_multirate(
+            self._h, G, Hn, _ptr(xs), _ptr(rf), *rf.shape, _iptr(rp), num_steps, _ptr(fh), _ptr(fa), _ptr(nz),
+            C.byref(m), _ptr(out["err"]), _iptr(out["best"]), _ptr(out["q"]), _ptr(out["u"]), _ptr(out["xpath"]),
+            _ptr(out["ee"]), _iptr(out["off"]), _ptr(out["fbest"]), _ptr(out["xcur"]), _ptr(out["xu_best"]),
+            _ptr(out["fhyp"])))
         return out
 
     # ---- the controller session (i7m_ctrl_begin / _step / _end) ----------------------------

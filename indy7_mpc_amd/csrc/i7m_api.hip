@@ -27,6 +27,7 @@
 #include "i7m_mpc_sampled.h"
 #include "i7m_ctrl.h"
 #include "i7m_mpc_multirate.h"
+#include "i7m_mpc_sampled_multirate.h"
 #include "i7m_plan.h"
 
 // Source hash of the tree this library was built from (__graft_entry__.build passes it), so
@@ -61,6 +62,8 @@ hipError_t i7m_prepare_sqp_fused(int dev, int N);
 
 // i7m_mpc_multirate_tu.hip (k_mpc_multirate_step in a unit of its own); args: const MultirateArgs*
 hipError_t i7m_launch_multirate_step(int n, hipStream_t s, const void* model, const void* args);
+// i7m_mpc_sampled_multirate_tu.hip (k_sampled_multirate_step); args: const SampledMultirateArgs*
+hipError_t i7m_launch_sampled_multirate_step(int ng, int H, hipStream_t s, const void* model, const void* args);
 
 static_assert(sizeof(i7m_problem_stats) == sizeof(ProblemStats), "stats layout");
 static_assert(ADMM_RES_MAX_N == ARES_N, "i7m_plan.h: k_admm_iter_res's horizon");
@@ -1982,6 +1985,202 @@ int i7m_mpc_run_tracking(i7m_handle* h, int32_t G, int32_t H, const double* xsta
                                       f_actual, err_out);
   return sampled_loop(h, "mpc_run_tracking", c, noise, err_out, best_out, q_out, ee_out, fbest_out, xcur_out,
                       xu_best_out, fhyp_out);
+}
+
+int i7m_sampled_multirate_opts_default(i7m_sampled_multirate_opts* o) {
+  if (!o) return fail(I7M_EINVAL, "null opts");
+  i7m_sampled_opts s;
+  (void)i7m_sampled_opts_default(&s);
+  o->sim_dt = s.sim_dt;
+  o->decay = s.decay;
+  o->frame = s.frame;
+  o->reset_what = s.reset_what;
+  o->keep_best = s.keep_best;
+  o->n_actual = s.n_actual;
+  o->shift_warm_start = 0;  // the reference's shift is commented out, src/gato_mpc_batch_sample.py:194-201
+  o->pad = 0;
+  return I7M_OK;
+}
+
+}  // extern "C"
+
+namespace {
+
+// The description of a multi-rate call of the family: describe_call with the options' shared fields.
+SampledCall describe_multirate_call(const i7m_handle* h, SampledKind kind, int G, int H, int num_steps,
+                                    const i7m_sampled_multirate_opts* opts, const GoalSource& goal, const double* xstart,
+                                    const double* fhyp, const double* f_actual, const double* hist_out) {
+  i7m_sampled_multirate_opts m;
+  (void)i7m_sampled_multirate_opts_default(&m);
+  if (opts) m = *opts;
+  const i7m_sampled_opts o{m.sim_dt, m.decay, m.frame, m.reset_what, m.keep_best, m.n_actual};
+  SampledCall c = describe_call(h, kind, G, H, num_steps, &o, goal, xstart, fhyp, f_actual, hist_out);
+  c.shift_warm_start = m.shift_warm_start;
+  return c;
+}
+
+// The multi-rate sampled-wrench closed loop of both entry points (`who` names the one in the
+// messages): sampled_loop with the plant split at knot boundaries (k_sampled_multirate_step) and,
+// in tracking mode, the window's schedule computed here (the knots completed so far).
+int sampled_multirate_loop(i7m_handle* h, const std::string& who, const SampledCall& c, const double* noise,
+                           double* dist_out, int32_t* best_out, double* q_out, double* u_out, double* xpath_out,
+                           double* ee_out, int32_t* off_out, double* fbest_out, double* xcur_out, double* xu_best_out,
+                           double* fhyp_out) {
+  if (h->ctrl.open) return session_open();
+  const int N = (int)h->N;
+  MultirateSchedule sch;
+  {
+    const char* which = "";
+    long at = 0;
+    if (!sampled_multirate_call_ok(c, N, &sch, &which, &at))
+      return fail(I7M_EINVAL, sampled_multirate_refusal(who, which, at, c, N));
+  }
+  const int G = c.G, H = c.H, num_steps = c.num_steps;
+  const i7m_sampled_opts& o = c.o;
+  const GoalSource& gs = c.goal;
+  const bool track = c.kind == SampledKind::tracking_multirate;
+  const std::vector<int32_t> offs = multirate_offsets(sch);
+  if (track && off_out)
+    for (int i = 0; i < num_steps; ++i) off_out[i] = offs[i];
+  if (G == 0) return I7M_OK;
+  int rc;
+  HIPCHK(hipSetDevice(h->dev));
+  const int B = G * H, n_sub = sch.total();
+  const size_t T = h->T;
+  const bool admm = h->cfg.qp_mode == I7M_QP_ADMM;
+  size_t bytes[SAMPLED_MULTIRATE_WS_COUNT];
+  sampled_multirate_ws_bytes(G, H, N, num_steps, n_sub, gs.n_endpoints, o.n_actual, noise != nullptr, gs.L, gs.ref_stride,
+                             gs.ref_phase != nullptr, bytes);
+  // host staging, declared first: alive until the workspace's final synchronize
+  const GroupStart start(h, G, H, c.xstart, gs);
+  Workspace ws(h, bytes);
+  if (!ws.base) return fail(I7M_ENOMEM, who + ": device allocation failed");
+  double *d_ep = ws.at<double>(SWS_EP), *d_xcur = ws.at<double>(SWS_XCUR), *d_xub = ws.at<double>(SWS_XUB),
+         *d_fact = ws.at<double>(SWS_FACT), *d_noise = bytes[SWS_NOISE] ? ws.at<double>(SWS_NOISE) : nullptr,
+         *d_dist = ws.at<double>(SWS_DIST), *d_q = ws.at<double>(SWS_Q), *d_fb = ws.at<double>(SWS_FB),
+         *d_rho0 = ws.at<double>(SWS_RHO0), *d_ref = track ? ws.at<double>(TWS_REF) : nullptr,
+         *d_ee = track ? ws.at<double>(TWS_EE) : nullptr, *d_u = ws.at<double>(SMWS_U),
+         *d_xp = ws.at<double>(SMWS_XPATH), *d_sub = ws.at<double>(SMWS_SUBDT);
+  int *d_best = ws.at<int>(SWS_BEST), *d_gi = ws.at<int>(SWS_GI), *d_alive = ws.at<int>(SWS_ALIVE),
+      *d_bh = ws.at<int>(SWS_BH), *d_phase = bytes[TWS_PHASE] ? ws.at<int>(TWS_PHASE) : nullptr;
+  const size_t hist = history_rows(num_steps, G);
+  // the start of i7m_mpc_run_sampled / _tracking, and the sub-step lengths
+  if ((rc = stage_start(h, start, gs, G, d_rho0, d_ref, d_phase))) return rc;
+  if ((rc = loop_instances(h, start.rows, gs.endpoints, gs.n_endpoints, d_ep, d_gi, d_alive))) return rc;
+  if ((rc = copy_in(h, d_xcur, c.xstart, (size_t)G * 12))) return rc;
+  if ((rc = copy_in(h, d_fact, c.f_actual, 6 * (size_t)o.n_actual * G))) return rc;
+  if (d_noise && (rc = copy_in(h, d_noise, noise, 3 * (size_t)num_steps * B))) return rc;
+  if (n_sub > 0 && (rc = copy_in(h, d_sub, sch.sub_dt.data(), (size_t)n_sub))) return rc;
+  HIPCHK(hipMemsetAsync(d_best, 0, 4 * (size_t)G, h->stream));  // the initial solve's XU_best is row 0
+  if ((rc = install_wrench(h, B, c.fhyp, o.frame))) return rc;
+  // the rows [lo, lo + n) (whole groups) through every MPC step on stream s, as sampled_loop's ranges
+  rc = run_ranges(h, B, [&](long lo, int n, hipStream_t s, StaggerMark* mark) -> int {
+    const long glo = lo / H;
+    const int ng = n / H;
+    double *xu = h->d_xu + lo * T, *out = h->d_out + lo * T, *xs = h->d_xs + lo * 12, *g = h->d_goal + lo * 3 * N;
+    auto reset = [&](int what) {
+      return admm && what ? admm_reset_rows(h, lo, n, what, s, d_rho0 + lo, hipMemcpyDeviceToDevice) : I7M_OK;
+    };
+    SampledMultirateArgs m{};
+    SampledArgs& a = m.S;
+    a.N = N;
+    a.H = H;
+    a.n_endpoints = gs.n_endpoints;
+    a.frame_world = o.frame == I7M_WRENCH_WORLD;
+    a.keep_best = o.keep_best != 0;
+    a.sim_dt = o.sim_dt;
+    a.decay = o.decay;
+    a.xs = xs;
+    a.XU = xu;
+    a.xu_new = out;
+    a.goals = g;
+    a.fext = h->d_fext + lo * 6;
+    a.xcur = d_xcur + glo * 12;
+    a.xub = d_xub + glo * T;
+    a.best = d_best + glo;
+    a.goal_idx = d_gi + glo;
+    a.alive = d_alive + glo;
+    a.endpoints = track ? nullptr : d_ep;
+    a.ref = d_ref;
+    a.ref_phase = d_phase ? d_phase + glo : nullptr;
+    a.L = (int)gs.L;
+    a.ref_stride = gs.ref_stride;
+    m.hist_stride = G;
+    int rc3;
+    if ((rc3 = reset(I7M_ADMM_RESET_ALL))) return rc3;
+    if ((rc3 = run_sqp(h, n, xu, out, xs, g, 3, nullptr, lo, s, mark))) return rc3;
+    // launch i: select(i - 1) (i = 0: the initial solve's row 0), then plant(i) ... goal(i);
+    // the last launch only selects
+    for (int i = 0; i <= num_steps; ++i) {
+      a.select = i == 0 ? 2 : 1;
+      a.plant = i < num_steps;
+      const size_t rec = ((size_t)std::max(i - 1, 0)) * G + glo, cur = (size_t)std::min(i, std::max(num_steps - 1, 0)) * G + glo;
+      a.noise = d_noise && i > 0 ? d_noise + ((size_t)(i - 1) * B + lo) * 3 : nullptr;
+      a.best_out = d_bh + rec;
+      a.fbest_out = d_fb + rec * 6;
+      a.f_actual = d_fact + ((size_t)(o.n_actual > 1 ? std::min(i, o.n_actual - 1) : 0) * G + glo) * 6;
+      a.dist_out = d_dist + cur;
+      a.q_out = d_q + cur * 6;
+      a.off = track && a.plant ? offs[i] : 0;
+      a.ee_out = track ? d_ee + cur * 3 : nullptr;
+      const int s0 = a.plant ? sch.sub_start[i] : 0;
+      m.n_sub = a.plant ? sch.sub_start[i + 1] - s0 : 0;
+      m.shift = a.plant && c.shift_warm_start ? sch.shift[i] : 0;
+      m.sub_dt = d_sub + s0;
+      m.u_out = d_u + cur * 6;
+      m.xpath_out = d_xp + ((size_t)s0 * G + glo) * 6;
+      HIPCHK(i7m_launch_sampled_multirate_step(ng, H, s, h->d_model, &m));
+      if (!a.plant) break;
+      if ((rc3 = reset(o.reset_what))) return rc3;
+      if ((rc3 = run_sqp(h, n, xu, out, xs, g, 3, nullptr, lo, s))) return rc3;
+    }
+    return I7M_OK;
+  }, stagger_cut_grouped(B, H));
+  if (rc) return rc;
+  if (num_steps > 0) {
+    if ((rc = copy_out(h, dist_out, d_dist, hist))) return rc;
+    if (q_out && (rc = copy_out(h, q_out, d_q, hist * 6))) return rc;
+    if (u_out && (rc = copy_out(h, u_out, d_u, hist * 6))) return rc;
+    if (xpath_out && (rc = copy_out(h, xpath_out, d_xp, (size_t)n_sub * G * 6))) return rc;
+    if (track && ee_out && (rc = copy_out(h, ee_out, d_ee, hist * 3))) return rc;
+    if (fbest_out && (rc = copy_out(h, fbest_out, d_fb, hist * 6))) return rc;
+    if (best_out) HIPCHK(hipMemcpyAsync(best_out, d_bh, 4 * hist, hipMemcpyDeviceToHost, h->stream));
+  }
+  if (xcur_out && (rc = copy_out(h, xcur_out, d_xcur, (size_t)G * 12))) return rc;
+  if (xu_best_out && (rc = copy_out(h, xu_best_out, d_xub, (size_t)G * T))) return rc;
+  if (fhyp_out && (rc = copy_out(h, fhyp_out, h->d_fext, (size_t)B * 6))) return rc;
+  return i7m_synchronize(h);
+}
+
+}  // namespace
+
+extern "C" {
+
+int i7m_mpc_run_sampled_multirate(i7m_handle* h, int32_t G, int32_t H, const double* xstart, const double* endpoints,
+                                  int32_t n_endpoints, int32_t num_steps, const double* fhyp, const double* f_actual,
+                                  const double* noise, const i7m_sampled_multirate_opts* opts, double* dist_out,
+                                  int32_t* best_out, double* q_out, double* u_out, double* xpath_out, double* fbest_out,
+                                  double* xcur_out, double* xu_best_out, double* fhyp_out) {
+  if (!h) return fail(I7M_EINVAL, "null handle");
+  const SampledCall c = describe_multirate_call(h, SampledKind::endpoints_multirate, G, H, num_steps, opts,
+                                                GoalSource::of_endpoints(endpoints, n_endpoints), xstart, fhyp, f_actual,
+                                                dist_out);
+  return sampled_multirate_loop(h, "mpc_run_sampled_multirate", c, noise, dist_out, best_out, q_out, u_out, xpath_out,
+                                nullptr, nullptr, fbest_out, xcur_out, xu_best_out, fhyp_out);
+}
+
+int i7m_mpc_run_tracking_multirate(i7m_handle* h, int32_t G, int32_t H, const double* xstart, const double* ref,
+                                   int32_t L, int32_t ref_stride, const int32_t* ref_phase, int32_t num_steps,
+                                   const double* fhyp, const double* f_actual, const double* noise,
+                                   const i7m_sampled_multirate_opts* opts, double* err_out, int32_t* best_out,
+                                   double* q_out, double* u_out, double* xpath_out, double* ee_out, int32_t* off_out,
+                                   double* fbest_out, double* xcur_out, double* xu_best_out, double* fhyp_out) {
+  if (!h) return fail(I7M_EINVAL, "null handle");
+  const SampledCall c = describe_multirate_call(h, SampledKind::tracking_multirate, G, H, num_steps, opts,
+                                                GoalSource::of_reference(ref, L, ref_stride, ref_phase, nullptr), xstart,
+                                                fhyp, f_actual, err_out);
+  return sampled_multirate_loop(h, "mpc_run_tracking_multirate", c, noise, err_out, best_out, q_out, u_out, xpath_out,
+                                ee_out, off_out, fbest_out, xcur_out, xu_best_out, fhyp_out);
 }
 
 }  // extern "C"

@@ -457,13 +457,17 @@ struct GoalSource {
 // (session): the handle's part, the sizes, the options, the goal source and the caller's required
 // pointers (hist_out: dist_out / err_out).  The session has no steps and reads neither sim_dt nor
 // n_actual; its start states are optional.
-enum class SampledKind { endpoints, tracking, session };
+// The multi-rate kinds (i7m_mpc_run_sampled_multirate / i7m_mpc_run_tracking_multirate): sim_dt is
+// finite and > 0 but not bounded by dt, shift_warm_start is 0 or 1, and the tracking window's
+// schedule is the library's (the knots completed), so no ref_offset is asked for.
+enum class SampledKind { endpoints, tracking, session, endpoints_multirate, tracking_multirate };
 struct SampledCall {
   SampledKind kind = SampledKind::endpoints;
   int qp_mode = I7M_QP_DIRECT, max_batch = 0;
   double dt = 0.0;
   int G = 0, H = 0, num_steps = 0;
   i7m_sampled_opts o{};
+  int shift_warm_start = 0;  // the multi-rate kinds only
   GoalSource goal;
   const double *xstart = nullptr, *fhyp = nullptr, *f_actual = nullptr;
   const double* hist_out = nullptr;
@@ -478,12 +482,16 @@ inline bool sampled_call_ok(const SampledCall& c, const char** which, long* at) 
     *at = a;
     return false;
   };
-  const bool loop = c.kind != SampledKind::session, track = c.kind != SampledKind::endpoints;
+  const bool multi = c.kind == SampledKind::endpoints_multirate || c.kind == SampledKind::tracking_multirate;
+  const bool loop = c.kind != SampledKind::session;
+  const bool track = c.kind != SampledKind::endpoints && c.kind != SampledKind::endpoints_multirate;
   const GoalSource& g = c.goal;
   if (c.qp_mode != I7M_QP_DIRECT && c.qp_mode != I7M_QP_ADMM) return no("qp_mode", c.qp_mode);
   if (c.H < 1 || c.H > 256 || (c.H & (c.H - 1))) return no("H", c.H);
   if (c.G < 0 || (long)c.G * c.H > c.max_batch) return no("G", (long)c.G * c.H);
-  if (loop && (!(c.o.sim_dt > 0.0) || !(c.o.sim_dt <= c.dt))) return no("sim_dt", 0);
+  if (loop && !multi && (!(c.o.sim_dt > 0.0) || !(c.o.sim_dt <= c.dt))) return no("sim_dt", 0);
+  if (multi && (!std::isfinite(c.o.sim_dt) || !(c.o.sim_dt > 0.0))) return no("sim_dt", 0);
+  if (multi && c.shift_warm_start != 0 && c.shift_warm_start != 1) return no("shift_warm_start", c.shift_warm_start);
   if (c.o.frame != I7M_WRENCH_LOCAL && c.o.frame != I7M_WRENCH_WORLD) return no("frame", c.o.frame);
   if (c.o.reset_what & ~I7M_ADMM_RESET_ALL) return no("reset_what", c.o.reset_what);
   if (!track && g.n_endpoints < 1) return no("n_endpoints", g.n_endpoints);
@@ -497,10 +505,10 @@ inline bool sampled_call_ok(const SampledCall& c, const char** which, long* at) 
   if (!c.fhyp) return no("fhyp", 0);
   if (loop && !c.f_actual) return no("f_actual", 0);
   if (loop && !c.hist_out) return no(track ? "err_out" : "dist_out", 0);
-  if (loop && track && c.num_steps > 0 && !g.ref_offset) return no("ref_offset", -1);
+  if (loop && track && !multi && c.num_steps > 0 && !g.ref_offset) return no("ref_offset", -1);
   for (int i = 0; track && g.ref_phase && i < c.G; ++i)
     if (g.ref_phase[i] < 0) return no("ref_phase", i);
-  for (int i = 0; loop && track && i < c.num_steps; ++i)
+  for (int i = 0; loop && track && !multi && i < c.num_steps; ++i)
     if (g.ref_offset[i] < 0) return no("ref_offset", i);
   return true;
 }
@@ -521,6 +529,48 @@ inline std::string sampled_refusal(const std::string& who, const std::string& wh
   if (which == "ref_offset" && at < 0) return who + ": null ref_offset with num_steps > 0";
   if (which == "ref_phase" || which == "ref_offset") return who + ": " + which + "[" + v + "] is negative";
   return who + ": null " + which;
+}
+
+// The multi-rate kinds' check: the family's (sampled_call_ok with a multi-rate kind: everything it
+// refuses for the single-rate loops but sim_dt > dt, and shift_warm_start), then the plant's
+// schedule for the handle's horizon N (multirate_schedule: *which = "shift" or "substeps", *at the
+// step).  On success *sch is the schedule the loop runs.
+inline bool sampled_multirate_call_ok(const SampledCall& c, int N, MultirateSchedule* sch, const char** which, long* at) {
+  *sch = MultirateSchedule{};
+  if (c.kind != SampledKind::endpoints_multirate && c.kind != SampledKind::tracking_multirate) {
+    *which = "kind";
+    *at = (long)c.kind;
+    return false;
+  }
+  if (!sampled_call_ok(c, which, at)) return false;
+  return multirate_schedule(c.dt, c.o.sim_dt, N, c.num_steps, sch, which, at);
+}
+// The text of a refusal by sampled_multirate_call_ok, for the entry point `who`.
+inline std::string sampled_multirate_refusal(const std::string& who, const std::string& which, long at,
+                                             const SampledCall& c, int N) {
+  if (which == "sim_dt" || which == "shift" || which == "substeps") return multirate_refusal(who, which, at, c.o.sim_dt, N);
+  if (which == "shift_warm_start") return who + ": shift_warm_start = " + std::to_string(at) + " is not 0 or 1";
+  if (which == "kind") return who + ": not a multi-rate call";
+  return sampled_refusal(who, which, at, c.max_batch);
+}
+// The window offsets of a multi-rate tracking run: off[i] = the knots completed by steps 0 .. i, the
+// notebook's eepos_offset after step i's plant.
+inline std::vector<int32_t> multirate_offsets(const MultirateSchedule& sch) {
+  std::vector<int32_t> off(sch.shift.size());
+  int32_t acc = 0;
+  for (size_t i = 0; i < off.size(); ++i) off[i] = (acc += sch.shift[i]);
+  return off;
+}
+// The multi-rate sampled loops' request: tracking_ws_bytes' sub-buffers, then the control history
+// (per step), the path (per sub-step) and the sub-step lengths.
+enum { SMWS_U = TRACKING_WS_COUNT, SMWS_XPATH, SMWS_SUBDT, SAMPLED_MULTIRATE_WS_COUNT };
+inline void sampled_multirate_ws_bytes(int G, int H, int N, int num_steps, int n_sub, int n_endpoints, int n_actual,
+                                       bool noise, long L, int ref_stride, bool phase,
+                                       size_t bytes[SAMPLED_MULTIRATE_WS_COUNT]) {
+  tracking_ws_bytes(G, H, N, num_steps, n_endpoints, n_actual, noise, L, ref_stride, phase, bytes);
+  bytes[SMWS_U] = 6 * 8 * history_rows(num_steps, G);
+  bytes[SMWS_XPATH] = 6 * 8 * history_rows(n_sub, G);
+  bytes[SMWS_SUBDT] = 8 * (size_t)std::max(n_sub, 1);
 }
 
 // i7m_ctrl_step's: the pointers, the clock, the offset, and a host scan of the measurement (a real

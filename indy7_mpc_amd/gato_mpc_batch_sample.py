@@ -12,8 +12,12 @@ What differs from the reference, on purpose:
   * the actual force is ``constant_f_ext`` for the whole run (zero if None), a WORLD-frame force
     like the hypotheses; the reference random-walks it every step (:244-250) and applies it to the
     plant as a joint-6 LOCAL force (:96-102) while it scores the hypotheses as world-frame ones;
-  * one rk4 step of ``sim_dt`` (<= dt) per control step (the reference's split at a knot boundary,
-    :170-187, never triggers then);
+  * with ``sim_dt <= dt``, one rk4 step of ``sim_dt`` per control step (``i7m_mpc_run_sampled``: the
+    reference's split at a knot boundary, :170-187, is left out there, and with it the float-residue
+    sub-step of 8.67e-19 s that the reference takes at every tenth step of sim_dt = 0.001);
+    with ``sim_dt > dt`` the plant step is split at the knot boundaries as the reference does
+    (``i7m_mpc_run_sampled_multirate``), xpath holds one q per plant sub-step and
+    ``control_inputs`` one control per logged step;
   * ``resample_f_ext=True`` perturbs every row but row 0 (:291-298: keep_best = 0, decay = 1);
     pass ``keep_best=True, decay=0.97`` for the controller's rule (gato_controller.py:120-129).
 
@@ -30,6 +34,23 @@ a reference trajectory, ``i7m_mpc_run_tracking``).  What differs from ``GATO_Con
     highest; tied hypotheses are identical rows, so the trajectories are the same;
   * the actual force is the caller's schedule (``f_actual``), not the controller's clipped random
     walk (:236-239).
+
+``run_mpc_fig8`` / ``run_fig8_groups`` are ``run_mpc_fig8`` of the reference's
+notebooks/gato_mpc_indy7_fig8.ipynb (``i7m_mpc_run_tracking_multirate``): the figure-8 tracking run
+under an unknown force, the plant stepped ``sim_dt`` per solve against the knot grid.  Kept: the
+split of a plant step at a knot boundary with its float residues, knot 0's control on every
+sub-step, the goal window advancing by the knots the plant completed (``eepos_offset``), no
+warm-start shift, the reset before every solve, the one-step scoring over the whole ``sim_dt``, the
+logging rule ``abs((i * sim_dt) % 0.05) < 1e-5`` with one control per logged step, the end of the
+run at the first step whose offset reaches ``L - 6 N`` (that step's plant is still in the path).
+What differs, besides the draws and the force schedule above:
+  * the actual force is a WORLD-frame force converted to joint 6's frame at every step's start
+    state, as src/gato_mpc_batch_sample.py:151-161 does; the notebook passes the world force as a
+    local one (its actInv is commented out);
+  * ties go to the lowest index, where the notebook's ``<=`` takes the highest; tied hypotheses are
+    identical rows;
+  * the notebook's resampling keeps f_best in row 1; here ``keep_best`` keeps it in the winning row
+    (gato_controller.py:120-129).
 """
 from __future__ import annotations
 
@@ -51,6 +72,29 @@ def tracking_schedule(sim_dt, sim_time, dt):
     sim_dt, sim_time, dt = (Fraction(repr(float(v))) for v in (sim_dt, sim_time, dt))
     num_steps = int(sim_time / sim_dt)
     return num_steps, np.array([int((i + 1) * sim_dt / dt) for i in range(num_steps)], dtype=np.int32)
+
+
+def logged_steps(num_steps, sim_dt):
+    """The steps the reference logs: abs((i * sim_dt) % 0.05) < 1e-5 (:236), in its float arithmetic."""
+    return np.array([i for i in range(num_steps) if abs((i * sim_dt) % 0.05) < 1e-5], dtype=int)
+
+
+def fig8_steps(dt, sim_dt, sim_time, N, L):
+    """(num_steps, full) of a figure-8 run over a reference of L points: full = the steps that reach
+    their solve (offset < L - 6 N, the notebook's bound), num_steps = full plus the step whose plant
+    still runs before the notebook breaks, int(sim_time / sim_dt) at most."""
+    most = int(sim_time / sim_dt)
+    off = np.cumsum(_lib.multirate_schedule(dt, sim_dt, most, N)[2])
+    over = np.flatnonzero(off >= L - 6 * N)
+    full = int(over[0]) if len(over) else most
+    return min(full + 1, most), full
+
+
+def _controls_after(r):
+    """(num_steps, G, 6) the control chosen by each step's solve and selection, XU_best[12:18] after
+    step i, which the reference logs (:240): it is the control the next step applies, and the last
+    step's is the final XU_best's."""
+    return np.concatenate([r["u"][1:], r["xu_best"][None, :, 12:18]], axis=0) if len(r["u"]) else r["u"]
 
 
 class MPC_GATO_Batch_Sample:
@@ -101,6 +145,8 @@ class MPC_GATO_Batch_Sample:
         G, H = xs.shape[0], self.batch_size
         num_steps = int(sim_time / sim_dt)
         fa, noise, h = self._run_inputs(G, num_steps, f_actual)
+        if sim_dt > self.dt:
+            return self._run_mpc_groups_multirate(h, xs, endpoints, num_steps, fa, noise, sim_dt)
         t0 = time.perf_counter()
         r = h.mpc_run_sampled(xs, endpoints, num_steps, np.tile(self.f_ext_batch, (G, 1)), fa, noise=noise,
                               sim_dt=sim_dt, frame="world", reset_what=_lib.ADMM_RESET_ALL, keep_best=self.keep_best,
@@ -121,6 +167,79 @@ class MPC_GATO_Batch_Sample:
         }
         self.last = r
         return xpaths, stats
+
+    def _run_mpc_groups_multirate(self, h, xs, endpoints, num_steps, fa, noise, sim_dt):
+        """run_mpc_groups with sim_dt > dt (i7m_mpc_run_sampled_multirate): the paths hold one q per
+        plant sub-step, control_inputs (logged, G, 6) one control per logged step."""
+        G, H = xs.shape[0], self.batch_size
+        t0 = time.perf_counter()
+        r = h.mpc_run_sampled_multirate(xs, endpoints, num_steps, np.tile(self.f_ext_batch, (G, 1)), fa, noise=noise,
+                                        sim_dt=sim_dt, frame="world", reset_what=_lib.ADMM_RESET_ALL,
+                                        keep_best=self.keep_best, decay=self.decay)
+        per_step = (time.perf_counter() - t0) / max(num_steps, 1)
+        self.f_ext_batch = r["fhyp"][:H].copy()
+        ran = np.isfinite(r["xpath"][:, :, 0])  # a group's path ends with the step it stopped at
+        xpaths = [[q for q in r["xpath"][ran[:, g], g]] for g in range(G)]
+        log = logged_steps(num_steps, sim_dt)
+        stats = {
+            "solve_times": [round(per_step, 5)] * len(log),  # the device loop's mean time per step
+            "goal_distances": np.round(r["dist"][log], 5),
+            "control_inputs": np.round(_controls_after(r)[log], 5),
+            "best_ids": r["best"],
+            "f_ext_best": r["fbest"],
+        }
+        self.last = r
+        return xpaths, stats
+
+    def run_fig8_groups(self, xstarts, fig8_traj, sim_dt=0.001, sim_time=5, f_actual=None, ref_phase=None):
+        """G independent controllers on the notebook's figure-8 run (i7m_mpc_run_tracking_multirate),
+        one per row of xstarts (G, 12), group g starting at point ref_phase[g] of the reference
+        (default 0).  fig8_traj: flat with six entries per point (as the notebook's figure8 builds
+        it), or (L, 3) / (L, 6).  The run has int(sim_time / sim_dt) steps at most and ends with the
+        first step whose window offset reaches L - 6 N (the notebook's bound): that step's plant is in
+        the paths, and it is not logged.  Returns (xpaths, stats): a list of G q-paths, one q per
+        plant sub-step, and the notebook's stats keys with a (logged steps, G) layout
+        (goal_distances (logged, G), control_inputs (logged, G, 6)) plus 'best_ids', 'f_ext_best'
+        and 'offsets' (every step)."""
+        xs = np.asarray(xstarts, float).reshape(-1, 12)
+        G, H = xs.shape[0], self.batch_size
+        ref = _sampling.reference_points(fig8_traj)
+        num_steps, full = fig8_steps(self.dt, sim_dt, sim_time, self.N, ref.shape[0])
+        fa, noise, h = self._run_inputs(G, num_steps, f_actual)
+        phase = None if ref_phase is None else np.asarray(ref_phase, dtype=np.int32).reshape(G)
+        t0 = time.perf_counter()
+        r = h.mpc_run_tracking_multirate(xs, ref, num_steps, np.tile(self.f_ext_batch, (G, 1)), fa, ref_phase=phase,
+                                         noise=noise, sim_dt=sim_dt, frame="world", reset_what=_lib.ADMM_RESET_ALL,
+                                         keep_best=self.keep_best, decay=self.decay)
+        per_step = (time.perf_counter() - t0) / max(num_steps, 1)
+        self.f_ext_batch = r["fhyp"][:H].copy()
+        xpaths = [[q for q in r["xpath"][:, g]] for g in range(G)]
+        log = logged_steps(full, sim_dt)  # the step the run ends at breaks before the notebook logs it
+        stats = {
+            "solve_times": [round(per_step, 5)] * len(log),  # the device loop's mean time per step
+            "goal_distances": np.round(r["err"][log], 5),
+            "control_inputs": np.round(_controls_after(r)[log], 5),
+            "best_ids": r["best"],
+            "f_ext_best": r["fbest"],
+            "offsets": r["off"],
+        }
+        self.last = r
+        return xpaths, stats
+
+    def run_mpc_fig8(self, xstart, fig8_traj, sim_dt=0.001, sim_time=5):
+        """One controller, as the notebook's run_mpc_fig8: (xpath, stats), xpath one q per plant
+        sub-step, the stats logged where abs((i * sim_dt) % 0.05) < 1e-5."""
+        xpaths, st = self.run_fig8_groups(np.asarray(xstart, float).reshape(1, 12), fig8_traj, sim_dt, sim_time)
+        self.xpath += xpaths[0]
+        stats = {
+            "solve_times": st["solve_times"],
+            "goal_distances": [float(d) for d in st["goal_distances"][:, 0]],
+            "control_inputs": [u for u in st["control_inputs"][:, 0]],
+            "best_ids": st["best_ids"][:, 0],
+            "f_ext_best": st["f_ext_best"][:, 0],
+            "offsets": st["offsets"],
+        }
+        return self.xpath, stats
 
     def run_tracking_groups(self, xstarts, ref_traj, sim_dt=0.01, sim_time=5, f_actual=None, ref_phase=None,
                             ref_offset=None):
@@ -167,13 +286,19 @@ class MPC_GATO_Batch_Sample:
 
     def run_mpc(self, xstart, endpoints, sim_dt=0.001, sim_time=5):
         """One controller, as the reference's run_mpc (src/gato_mpc_batch_sample.py:106-252):
-        (xpath, stats), xpath one q per control step until the final goal is reached."""
+        (xpath, stats), xpath one q per control step (sim_dt > dt: per plant sub-step) until the
+        final goal is reached."""
         xpaths, st = self.run_mpc_groups(np.asarray(xstart, float).reshape(1, 12), endpoints, sim_dt, sim_time)
         self.xpath += xpaths[0]
+        if sim_dt > self.dt:
+            keep = np.isfinite(st["goal_distances"][:, 0])
+            controls = [u for u in st["control_inputs"][keep, 0]]
+        else:
+            controls = [st["control_inputs"][0][0]]
         stats = {
             "solve_times": st["solve_times"],
             "goal_distances": [float(d) for d in st["goal_distances"][:, 0] if np.isfinite(d)],
-            "control_inputs": [st["control_inputs"][0][0]],
+            "control_inputs": controls,
             "best_ids": st["best_ids"][:, 0],
             "f_ext_best": st["f_ext_best"][:, 0],
         }
