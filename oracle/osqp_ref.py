@@ -276,8 +276,9 @@ class SQPRef:
 
     ALPHAS = np.array([1.0, 0.5, 0.25, 0.125, 0.0625, 0.03125, 0.015625, 0.0078125])
 
-    def __init__(self, solver: OSQPSolverRef, stats=None):
+    def __init__(self, solver: OSQPSolverRef, stats=None, max_iters=2, mu=10.0, step_tol=1e-3):
         self.solver = solver
+        self.max_iters, self.mu, self.step_tol = max_iters, mu, step_tol
         self.stats = stats or {
             "qp_iters": {"values": [], "unit": "", "multiplier": 1},
             "linesearch_alphas": {"values": [], "unit": "", "multiplier": 1},
@@ -323,7 +324,7 @@ class SQPRef:
     def merit_terms(self, XU, XU_ref, goals):
         q, v, u = self.eepos_cost(goals, XU)
         cv = self.integrator_err(XU) + np.linalg.norm(XU[: self.solver.nx] - XU_ref[: self.solver.nx])
-        return q + v + u + 10.0 * cv
+        return q + v + u + self.mu * cv
 
     # src/osqp_sqp.py:49-74
     def linesearch(self, XU, XU_fullstep, eepos_goals, record=None):
@@ -346,7 +347,7 @@ class SQPRef:
     # src/osqp_sqp.py:76-93
     def sqp(self, xcur, eepos_goals, XU, record=None):
         qp = 0
-        for qp in range(2):
+        for qp in range(self.max_iters):
             sol = self.solver.setup_and_solve_qp(XU, xcur, eepos_goals)
             if record is not None:
                 record.append(dict(sol=sol.x.copy()))
@@ -357,7 +358,7 @@ class SQPRef:
             XU = XU + step
             stepsize = np.linalg.norm(step)
             self.stats["sqp_stepsizes"]["values"].append(stepsize)
-            if stepsize < 1e-3:
+            if stepsize < self.step_tol:
                 break
         self.stats["qp_iters"]["values"].append(qp + 1)
         return XU

@@ -24,6 +24,7 @@ import pytest
 
 from oracle import cpu
 from oracle.osqp_ref import synthetic_batch
+from settings_cases import choose_step_tol
 
 pytestmark = pytest.mark.gpu
 GOLD = os.path.join(os.path.dirname(__file__), "golden", "notebook_kats.json")
@@ -375,25 +376,39 @@ KERNELS = (("res", {"I7M_ADMM_RES": "1", "I7M_ADMM_ITER2": "-1"}),
            ("iter4", {"I7M_ADMM_RES": "0", "I7M_ADMM_ITER2": "0"}))
 
 
-@pytest.mark.parametrize("B,N,admm", [(13, 32, None), (600, 32, None), (1, 32, None), (13, 16, None),
-                                      (13, 32, {"max_iter": 20})])
-def test_admm_iteration_kernels_bit_identical(lib, model, monkeypatch, B, N, admm):
+@pytest.mark.parametrize("B,N,admm,sqp", [
+    (13, 32, None, None), (600, 32, None, None), (1, 32, None, None), (13, 16, None, None),
+    (13, 32, {"max_iter": 20}, None),
+    (13, 16, {"check_termination": 7, "scaling": 3, "alpha": 1.2, "sigma": 1e-4}, None),
+    (13, 16, None, {"max_sqp_iters": 5, "step_tol": "chosen"}),
+], ids=["13-32-None", "600-32-None", "1-32-None", "13-16-None", "13-32-admm4", "13-16-osqp_settings", "13-16-sqp5_ragged"])
+def test_admm_iteration_kernels_bit_identical(lib, model, monkeypatch, B, N, admm, sqp):
     """The three OSQP iteration kernels run the same arithmetic per problem: k_admm_iter_res (one
     problem per workgroup, LDS-resident: launches of <= 256 problems at N <= 32), k_admm_iter2 (two
     per wave: <= 512) and k_admm_iter (four), each forced (I7M_ADMM_RES, I7M_ADMM_ITER2): two
     consecutive solves are equal bit for bit, carried state, OSQP records and statuses included
-    (B = 13: empty rows in the streaming kernels' last wave; max_iter 20: the closing tests)."""
+    (B = 13: empty rows in the streaming kernels' last wave; max_iter 20: the closing tests;
+    osqp_settings: a check interval, scaling passes, alpha and sigma off their defaults;
+    sqp5_ragged: five SQP iterations with a step_tol, chosen from the port's step lengths
+    (settings_cases.choose_step_tol), that stops some rows of a wave while their neighbours
+    iterate on)."""
     xcur, goals, XU = synthetic_batch(B, N, 54)
+    sqp = dict(sqp or {})
+    if sqp.get("step_tol") == "chosen":
+        steps = cpu.solve_admm(xcur, goals, XU, N, cpu.AdmmState(B, N), max_iters=sqp["max_sqp_iters"], step_tol=0.0)[3]
+        sqp["step_tol"] = choose_step_tol(steps)
     res = []
     for _, env in KERNELS:
         for k, v in env.items():
             monkeypatch.setenv(k, v)
         kw = {"admm": admm} if admm else {}
-        h = lib.Handle(model, N=N, max_batch=B, qp_mode=lib.QP_ADMM, **kw)
-        o1, _ = h.solve(xcur, goals, XU)
+        h = lib.Handle(model, N=N, max_batch=B, qp_mode=lib.QP_ADMM, **kw, **sqp)
+        o1, s1 = h.solve(xcur, goals, XU)
         o2, _ = h.solve(xcur, goals, o1)
         res.append((o1, o2) + h.admm_state(B) + h.admm_stats(B, with_status=True))
         h.close()
+        if "step_tol" in sqp:
+            assert len(set(s1["qp_iters"].tolist())) >= 3, s1["qp_iters"]  # rows of one wave stop at different iterations
     for other in res[1:]:
         for a, b in zip(res[0], other):
             np.testing.assert_array_equal(a, b)

@@ -253,16 +253,23 @@ def test_closed_loop_500_steps_admm_default_shadowed_by_port(lib, model):
 
 class _PortAdmmSQP:
     """run_mpc_ref's `sqp` with every solve by the C++ port's ADMM mode, the OSQP state carried from
-    call to call (one instance: the reference's single osqp.OSQP object, src/osqp_solver.py:38-40)."""
+    call to call (one instance: the reference's single osqp.OSQP object, src/osqp_solver.py:38-40).  admm:
+    OSQP settings (oracle/cpu.py::admm_cfg's keywords), cfg: the port's SQP settings (max_iters, mu,
+    step_tol, ...); qp_iters / steps: every solve's SQP iteration count and step lengths."""
 
-    def __init__(self, N=32):
+    def __init__(self, N=32, admm=None, **cfg):
         from oracle import cpu
         self.cpu, self.solver, self.N = cpu, OSQPSolverRef(N=N), N
-        self.state = cpu.AdmmState(1, N)
+        self.admm, self.cfg = (cpu.admm_cfg(**admm) if admm else None), cfg
+        self.state = cpu.AdmmState(1, N, rho=(admm or {}).get("rho", 0.1))
+        self.qp_iters, self.steps = [], []
 
     def sqp(self, xcur, goal, XU):
-        out, *_ = self.cpu.solve_admm(np.asarray(xcur, float)[None], np.asarray(goal, float)[None],
-                                      np.asarray(XU, float)[None], self.N, self.state)
+        out, qp, _, steps, _ = self.cpu.solve_admm(np.asarray(xcur, float)[None], np.asarray(goal, float)[None],
+                                                   np.asarray(XU, float)[None], self.N, self.state, admm=self.admm,
+                                                   **self.cfg)
+        self.qp_iters.append(int(qp[0]))
+        self.steps.append(steps[0])
         return out[0]
 
 
