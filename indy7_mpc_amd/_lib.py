@@ -612,52 +612,6 @@ class Handle:
                 raise ValueError(f"noise must be ({num_steps}, {G * Hn}, 3)")
         return xs, G, fh, Hn, fa, nz, self._opts(frame, reset_what, keep_best, decay, sim_dt, fa.shape[0])
 
-    def mpc_run_sampled(self, xstart, endpoints, num_steps, fhyp, f_actual, noise=None, sim_dt=0.001, frame="world",
-                        reset_what=ADMM_RESET_ALL, keep_best=False, decay=1.0):
-        """Sampled-wrench closed loop of G controllers with H hypotheses each on the device
-        (i7m_mpc_run_sampled): xstart (G, 12), endpoints (E, 3), fhyp (G * H, 6) with group g owning
-        rows [g H, (g + 1) H), f_actual (G, 6) held for the run or (num_steps, G, 6), noise
-        (num_steps, G * H, 3) or None (no resampling).  Returns a dict: dist (num_steps, G), best
-        (num_steps, G) int32, q and fbest (num_steps, G, 6), xcur (G, 12), xu_best (G, T), fhyp
-        (G * H, 6) the final hypotheses (also left set on the handle, in `frame`)."""
-        ep = _f64(endpoints).reshape(-1, 3)
-        num_steps = int(num_steps)
-        xs, G, fh, Hn, fa, nz, o = self._sampled_inputs(xstart, num_steps, fhyp, f_actual, noise, sim_dt, frame,
-                                                         reset_what, keep_best, decay)
-        out = dict(dist=np.empty((num_steps, G)), best=np.empty((num_steps, G), dtype=np.int32),
-                   q=np.empty((num_steps, G, NJ)), fbest=np.empty((num_steps, G, 6)), xcur=np.empty((G, NX)),
-                   xu_best=np.empty((G, self.T)), fhyp=np.empty((G * Hn, 6)))
-        _check(self._lib.i7m_mpc_run_sampled(self._h, G, Hn, _ptr(xs), _ptr(ep), ep.shape[0], num_steps, _ptr(fh),
-                                             _ptr(fa), _ptr(nz), C.byref(o), _ptr(out["dist"]), _iptr(out["best"]),
-                                             _ptr(out["q"]), _ptr(out["fbest"]), _ptr(out["xcur"]),
-                                             _ptr(out["xu_best"]), _ptr(out["fhyp"])))
-        return out
-
-    def mpc_run_tracking(self, xstart, ref, ref_offset, fhyp, f_actual, ref_phase=None, noise=None, sim_dt=0.01,
-                         frame="world", reset_what=ADMM_RESET_ALL, keep_best=False, decay=1.0):
-        """The sampled-wrench closed loop tracking a reference trajectory (i7m_mpc_run_tracking):
-        ref (L, 3) or (L, 6) (the first three of each point read), ref_offset (num_steps,) the
-        window's offset at every step, ref_phase (G,) the groups' start points on the reference or
-        None; the rest as mpc_run_sampled.  At step i every row of group g is solved against
-        ref[min(phase[g] + ref_offset[i] + k, L - 1)], k = 0 .. N-1.  Returns a dict: err
-        (num_steps, G) the distance of the EE to the window's first point, best, q, ee
-        (num_steps, G, 3), fbest, xcur, xu_best, fhyp."""
-        rf = self._reference(ref)
-        ro = np.ascontiguousarray(ref_offset, dtype=np.int32).reshape(-1)
-        num_steps = ro.shape[0]
-        xs, G, fh, Hn, fa, nz, o = self._sampled_inputs(xstart, num_steps, fhyp, f_actual, noise, sim_dt, frame,
-                                                         reset_what, keep_best, decay)
-        rp = self._phases(ref_phase, G)
-        out = dict(err=np.empty((num_steps, G)), best=np.empty((num_steps, G), dtype=np.int32),
-                   q=np.empty((num_steps, G, NJ)), ee=np.empty((num_steps, G, 3)), fbest=np.empty((num_steps, G, 6)),
-                   xcur=np.empty((G, NX)), xu_best=np.empty((G, self.T)), fhyp=np.empty((G * Hn, 6)))
-        _check(self._lib.i7m_mpc_run_tracking(self._h, G, Hn, _ptr(xs), _ptr(rf), *rf.shape, _iptr(rp), _iptr(ro),
-                                              num_steps, _ptr(fh), _ptr(fa), _ptr(nz), C.byref(o), _ptr(out["err"]),
-                                              _iptr(out["best"]), _ptr(out["q"]), _ptr(out["ee"]),
-                                              _ptr(out["fbest"]), _ptr(out["xcur"]), _ptr(out["xu_best"]),
-                                              _ptr(out["fhyp"])))
-        return out
-
     def _multirate_opts(self, o, shift_warm_start):
         """The multi-rate options struct from the family's (same fields first) and the shift flag."""
         m = i7m_sampled_multirate_opts()
@@ -677,6 +631,67 @@ class Handle:
             raise I7MError(f"the library plans {n_sub.value} sub-steps, this binding {sub_start[-1]}")
         return n_sub.value, sub_start, shift
 
+    def _run_family(self, xstart, num_steps, fhyp, f_actual, noise, sim_dt, frame, reset_what, keep_best, decay,
+                    endpoints=None, ref=None, ref_phase=None, ref_offset=None, shift_warm_start=None):
+        """The four loops of the family behind one marshalling: the goal source is `endpoints`, or
+        `ref` with `ref_phase` and (single-rate plant) `ref_offset`; the plant is multi-rate where
+        shift_warm_start is given.  The returned dict holds the entry point's outputs in the order of
+        its C arguments, then a multi-rate run's schedule."""
+        track, multi = ref is not None, shift_warm_start is not None
+        if track:
+            rf = self._reference(ref)
+        else:
+            ep = _f64(endpoints).reshape(-1, 3)
+        xs, G, fh, Hn, fa, nz, o = self._sampled_inputs(xstart, num_steps, fhyp, f_actual, noise, sim_dt, frame,
+                                                         reset_what, keep_best, decay)
+        if track:
+            rp = self._phases(ref_phase, G)
+            goal = [_ptr(rf), *rf.shape, _iptr(rp)] + ([] if multi else [_iptr(ref_offset)])
+        else:
+            goal = [_ptr(ep), ep.shape[0]]
+        out = {"err" if track else "dist": np.empty((num_steps, G)), "best": np.empty((num_steps, G), dtype=np.int32),
+               "q": np.empty((num_steps, G, NJ))}
+        if multi:
+            o = self._multirate_opts(o, shift_warm_start)
+            n_sub, sub_start, shift = self._multirate_plan(sim_dt, num_steps)
+            out.update(u=np.empty((num_steps, G, NU)), xpath=np.empty((n_sub, G, NJ)))
+        if track:
+            out["ee"] = np.empty((num_steps, G, 3))
+        if track and multi:
+            out["off"] = np.empty(num_steps, dtype=np.int32)
+        out.update(fbest=np.empty((num_steps, G, 6)), xcur=np.empty((G, NX)), xu_best=np.empty((G, self.T)),
+                   fhyp=np.empty((G * Hn, 6)))
+        fn = getattr(self._lib, "i7m_mpc_run_" + ("tracking" if track else "sampled") + ("_multirate" if multi else ""))
+        _check(fn(self._h, G, Hn, _ptr(xs), *goal, num_steps, _ptr(fh), _ptr(fa), _ptr(nz), C.byref(o),
+                  *[(_iptr if v.dtype == np.int32 else _ptr)(v) for v in out.values()]))
+        if multi:
+            out.update(sub_start=sub_start, shift=shift)
+        return out
+
+    def mpc_run_sampled(self, xstart, endpoints, num_steps, fhyp, f_actual, noise=None, sim_dt=0.001, frame="world",
+                        reset_what=ADMM_RESET_ALL, keep_best=False, decay=1.0):
+        """Sampled-wrench closed loop of G controllers with H hypotheses each on the device
+        (i7m_mpc_run_sampled): xstart (G, 12), endpoints (E, 3), fhyp (G * H, 6) with group g owning
+        rows [g H, (g + 1) H), f_actual (G, 6) held for the run or (num_steps, G, 6), noise
+        (num_steps, G * H, 3) or None (no resampling).  Returns a dict: dist (num_steps, G), best
+        (num_steps, G) int32, q and fbest (num_steps, G, 6), xcur (G, 12), xu_best (G, T), fhyp
+        (G * H, 6) the final hypotheses (also left set on the handle, in `frame`)."""
+        return self._run_family(xstart, int(num_steps), fhyp, f_actual, noise, sim_dt, frame, reset_what, keep_best, decay,
+                                endpoints=endpoints)
+
+    def mpc_run_tracking(self, xstart, ref, ref_offset, fhyp, f_actual, ref_phase=None, noise=None, sim_dt=0.01,
+                         frame="world", reset_what=ADMM_RESET_ALL, keep_best=False, decay=1.0):
+        """The sampled-wrench closed loop tracking a reference trajectory (i7m_mpc_run_tracking):
+        ref (L, 3) or (L, 6) (the first three of each point read), ref_offset (num_steps,) the
+        window's offset at every step, ref_phase (G,) the groups' start points on the reference or
+        None; the rest as mpc_run_sampled.  At step i every row of group g is solved against
+        ref[min(phase[g] + ref_offset[i] + k, L - 1)], k = 0 .. N-1.  Returns a dict: err
+        (num_steps, G) the distance of the EE to the window's first point, best, q, ee
+        (num_steps, G, 3), fbest, xcur, xu_best, fhyp."""
+        ro = np.ascontiguousarray(ref_offset, dtype=np.int32).reshape(-1)
+        return self._run_family(xstart, ro.shape[0], fhyp, f_actual, noise, sim_dt, frame, reset_what, keep_best, decay,
+                                ref=ref, ref_phase=ref_phase, ref_offset=ro)
+
     def mpc_run_sampled_multirate(self, xstart, endpoints, num_steps, fhyp, f_actual, noise=None, sim_dt=0.001,
                                   frame="world", reset_what=ADMM_RESET_ALL, keep_best=False, decay=1.0,
                                   shift_warm_start=0):
@@ -686,21 +701,8 @@ class Handle:
         completes.  Returns mpc_run_sampled's dict plus u (num_steps, G, 6) the control applied at
         each step, xpath (n_sub, G, 6) one q per plant sub-step, and the schedule: sub_start
         (num_steps + 1,), shift (num_steps,)."""
-        ep = _f64(endpoints).reshape(-1, 3)
-        num_steps = int(num_steps)
-        xs, G, fh, Hn, fa, nz, o = self._sampled_inputs(xstart, num_steps, fhyp, f_actual, noise, sim_dt, frame,
-                                                         reset_what, keep_best, decay)
-        m = self._multirate_opts(o, shift_warm_start)
-        n_sub, sub_start, shift = self._multirate_plan(sim_dt, num_steps)
-        out = dict(dist=np.empty((num_steps, G)), best=np.empty((num_steps, G), dtype=np.int32),
-                   q=np.empty((num_steps, G, NJ)), u=np.empty((num_steps, G, NU)), xpath=np.empty((n_sub, G, NJ)),
-                   fbest=np.empty((num_steps, G, 6)), xcur=np.empty((G, NX)), xu_best=np.empty((G, self.T)),
-                   fhyp=np.empty((G * Hn, 6)), sub_start=sub_start, shift=shift)
-        _check(self._lib.i7m_mpc_run_sampled_multirate(
-            self._h, G, Hn, _ptr(xs), _ptr(ep), ep.shape[0], num_steps, _ptr(fh), _ptr(fa), _ptr(nz), C.byref(m),
-            _ptr(out["dist"]), _iptr(out["best"]), _ptr(out["q"]), _ptr(out["u"]), _ptr(out["xpath"]),
-            _ptr(out["fbest"]), _ptr(out["xcur"]), _ptr(out["xu_best"]), _ptr(out["fhyp"])))
-        return out
+        return self._run_family(xstart, int(num_steps), fhyp, f_actual, noise, sim_dt, frame, reset_what, keep_best, decay,
+                                endpoints=endpoints, shift_warm_start=shift_warm_start)
 
     def mpc_run_tracking_multirate(self, xstart, ref, num_steps, fhyp, f_actual, ref_phase=None, noise=None,
                                    sim_dt=0.02, frame="world", reset_what=ADMM_RESET_ALL, keep_best=False, decay=1.0,
@@ -709,24 +711,8 @@ class Handle:
         offset at step i is the number of knots the plant has completed by then (the notebook's
         eepos_offset), computed by the library.  Returns mpc_run_tracking's dict plus u, xpath, off
         (num_steps,) int32 those offsets, sub_start and shift."""
-        rf = self._reference(ref)
-        num_steps = int(num_steps)
-        xs, G, fh, Hn, fa, nz, o = self._sampled_inputs(xstart, num_steps, fhyp, f_actual, noise, sim_dt, frame,
-                                                         reset_what, keep_best, decay)
-        rp = self._phases(ref_phase, G)
-        m = self._multirate_opts(o, shift_warm_start)
-        n_sub, sub_start, shift = self._multirate_plan(sim_dt, num_steps)
-        out = dict(err=np.empty((num_steps, G)), best=np.empty((num_steps, G), dtype=np.int32),
-                   q=np.empty((num_steps, G, NJ)), u=np.empty((num_steps, G, NU)), xpath=np.empty((n_sub, G, NJ)),
-                   ee=np.empty((num_steps, G, 3)), off=np.empty(num_steps, dtype=np.int32),
-                   fbest=np.empty((num_steps, G, 6)), xcur=np.empty((G, NX)), xu_best=np.empty((G, self.T)),
-                   fhyp=np.empty((G * Hn, 6)), sub_start=sub_start, shift=shift)
-        _check(self._lib.i7m_mpc_run_tracking_multirate(
-            self._h, G, Hn, _ptr(xs), _ptr(rf), *rf.shape, _iptr(rp), num_steps, _ptr(fh), _ptr(fa), _ptr(nz),
-            C.byref(m), _ptr(out["err"]), _iptr(out["best"]), _ptr(out["q"]), _ptr(out["u"]), _ptr(out["xpath"]),
-            _ptr(out["ee"]), _iptr(out["off"]), _ptr(out["fbest"]), _ptr(out["xcur"]), _ptr(out["xu_best"]),
-            _ptr(out["fhyp"])))
-        return out
+        return self._run_family(xstart, int(num_steps), fhyp, f_actual, noise, sim_dt, frame, reset_what, keep_best, decay,
+                                ref=ref, ref_phase=ref_phase, shift_warm_start=shift_warm_start)
 
     # ---- the controller session (i7m_ctrl_begin / _step / _end) ----------------------------
     def ctrl_begin(self, ref, fhyp, x0=None, groups=None, ref_phase=None, frame="world", reset_what=ADMM_RESET_ALL,

@@ -981,6 +981,12 @@ int admm_reset_rows(i7m_handle* h, long lo, long n, int what, hipStream_t s, con
   if (what & I7M_ADMM_RESET_RHO) HIPCHK(hipMemcpyAsync(a.srho, rho, (size_t)n * 8, kind, s));
   return I7M_OK;
 }
+// A closed loop's reset before a solve: rows [lo, lo + n) afresh on stream s, their rho from the
+// run's initial values d_rho0 (row 0 first).  Nothing outside I7M_QP_ADMM or for what = 0.
+int loop_reset(i7m_handle* h, long lo, long n, int what, hipStream_t s, const double* d_rho0) {
+  if (h->cfg.qp_mode != I7M_QP_ADMM || !what) return I7M_OK;
+  return admm_reset_rows(h, lo, n, what, s, d_rho0 + lo, hipMemcpyDeviceToDevice);
+}
 
 // One closed-loop call's device memory beyond the handle's: a Carved (base null: the allocation
 // failed) whose destructor synchronises the handle's stream before it frees, so on every return,
@@ -1729,7 +1735,6 @@ int i7m_mpc_run_multirate(i7m_handle* h, int32_t B, const double* xstart, const 
   HIPCHK(hipSetDevice(h->dev));
   const size_t T = h->T;
   const int n_sub = sch.total();
-  const bool admm = h->cfg.qp_mode == I7M_QP_ADMM;
   size_t bytes[MULTIRATE_WS_COUNT];
   multirate_ws_bytes(B, n_endpoints, num_steps, n_sub, bytes);
   // host staging, declared first: alive until the workspace's final synchronize
@@ -1750,10 +1755,6 @@ int i7m_mpc_run_multirate(i7m_handle* h, int32_t B, const double* xstart, const 
   // the instances [lo, lo + n) through every MPC step on stream s, as i7m_mpc_run's ranges
   rc = run_ranges(h, B, [&](long lo, int n, hipStream_t s, StaggerMark* mark) -> int {
     double *xu = h->d_xu + lo * T, *out = h->d_out + lo * T, *xs = h->d_xs + lo * 12, *g = h->d_goal + lo * 3 * N;
-    // the solver state of these instances afresh, asynchronous on s (ADMM mode)
-    auto reset = [&](int what) {
-      return admm && what ? admm_reset_rows(h, lo, n, what, s, d_rho0 + lo, hipMemcpyDeviceToDevice) : I7M_OK;
-    };
     MultirateArgs a{};
     a.N = N;
     a.n_endpoints = n_endpoints;
@@ -1768,10 +1769,10 @@ int i7m_mpc_run_multirate(i7m_handle* h, int32_t B, const double* xstart, const 
     a.goal_idx = d_gi + lo;
     a.alive = d_alive + lo;
     int rc3;
-    if ((rc3 = reset(I7M_ADMM_RESET_ALL))) return rc3;
+    if ((rc3 = loop_reset(h, lo, n, I7M_ADMM_RESET_ALL, s, d_rho0))) return rc3;
     if ((rc3 = run_sqp(h, n, xu, xu, xs, g, 3, nullptr, lo, s, mark))) return rc3;
     for (int i = 0; i < num_steps; ++i) {
-      if ((rc3 = reset(o.reset_what))) return rc3;
+      if ((rc3 = loop_reset(h, lo, n, o.reset_what, s, d_rho0))) return rc3;
       // xu_new = sqp(xcur, goal, XU) into the scratch buffer d_out (XU itself is read only)
       if ((rc3 = run_sqp(h, n, xu, out, xs, g, 3, nullptr, lo, s))) return rc3;
       a.n_sub = sch.sub_start[i + 1] - sch.sub_start[i];
@@ -1812,10 +1813,11 @@ int i7m_sampled_opts_default(i7m_sampled_opts* o) {
 
 namespace {
 
-// The description of a call of the sampled-wrench family on this handle (i7m_plan.h).
+// The description of a call of the sampled-wrench family on this handle (i7m_plan.h).  opts: the
+// options every kind shares (null: the defaults); shift_warm_start: the multi-rate kinds' flag.
 SampledCall describe_call(const i7m_handle* h, SampledKind kind, int G, int H, int num_steps, const i7m_sampled_opts* opts,
-                          const GoalSource& goal, const double* xstart, const double* fhyp, const double* f_actual,
-                          const double* hist_out) {
+                          int shift_warm_start, const GoalSource& goal, const double* xstart, const double* fhyp,
+                          const double* f_actual, const double* hist_out) {
   SampledCall c;
   c.kind = kind;
   c.qp_mode = h->cfg.qp_mode;
@@ -1826,6 +1828,7 @@ SampledCall describe_call(const i7m_handle* h, SampledKind kind, int G, int H, i
   c.num_steps = num_steps;
   (void)i7m_sampled_opts_default(&c.o);
   if (opts) c.o = *opts;
+  c.shift_warm_start = shift_warm_start;
   c.goal = goal;
   c.xstart = xstart;
   c.fhyp = fhyp;
@@ -1833,38 +1836,59 @@ SampledCall describe_call(const i7m_handle* h, SampledKind kind, int G, int H, i
   c.hist_out = hist_out;
   return c;
 }
-// The family's one argument check (sampled_call_ok), before the device is touched and before any
-// handle state changes.
-int check_call(const std::string& who, const SampledCall& c) {
+// The family's one argument check, before the device is touched and before any handle state
+// changes: sampled_call_ok, or for a multi-rate kind sampled_multirate_call_ok, which also leaves
+// the plant's schedule for the handle's horizon in *sch (untouched for the other kinds).
+int check_call(const std::string& who, const SampledCall& c, int N, MultirateSchedule* sch) {
   const char* which = "";
   long at = 0;
+  if (multirate_kind(c.kind)) {
+    if (sampled_multirate_call_ok(c, N, sch, &which, &at)) return I7M_OK;
+    return fail(I7M_EINVAL, sampled_multirate_refusal(who, which, at, c, N));
+  }
   if (sampled_call_ok(c, &which, &at)) return I7M_OK;
   return fail(I7M_EINVAL, sampled_refusal(who, which, at, c.max_batch));
 }
 
-// The sampled-wrench closed loop of both entry points (`who` names the one in the messages).
-// ee_out: the tracking mode's EE history, null in endpoint mode.
-int sampled_loop(i7m_handle* h, const std::string& who, const SampledCall& c, const double* noise, double* dist_out,
-                 int32_t* best_out, double* q_out, double* ee_out, double* fbest_out, double* xcur_out,
-                 double* xu_best_out, double* fhyp_out) {
+// Where a loop of the family leaves its results (host, each but hist may be null): the histories
+// per step (hist: dist_out / err_out; ee: the tracking kinds'; u, xpath, off: the multi-rate kinds')
+// and the final state.
+struct SampledOut {
+  double* hist = nullptr;
+  int32_t* best = nullptr;
+  double *q = nullptr, *u = nullptr, *xpath = nullptr, *ee = nullptr;
+  int32_t* off = nullptr;
+  double *fbest = nullptr, *xcur = nullptr, *xu_best = nullptr, *fhyp = nullptr;
+};
+
+// The sampled-wrench closed loop of the family's four entry points (`who` names the one in the
+// messages).  A multi-rate kind owns the plant's schedule and the tracking window's offsets derived
+// from it (the knots completed so far), splits the plant at knot boundaries
+// (k_sampled_multirate_step) and records u and the path; a single-rate kind has neither, reads the
+// caller's ref_offset and launches k_sampled_step.
+int sampled_loop(i7m_handle* h, const std::string& who, const SampledCall& c, const double* noise, const SampledOut& out) {
   if (h->ctrl.open) return session_open();
+  const int N = (int)h->N;
+  const bool multi = multirate_kind(c.kind), track = tracking_kind(c.kind);
+  MultirateSchedule sch;
   int rc;
-  if ((rc = check_call(who, c))) return rc;
+  if ((rc = check_call(who, c, N, &sch))) return rc;
   const int G = c.G, H = c.H, num_steps = c.num_steps;
   const i7m_sampled_opts& o = c.o;
   const GoalSource& gs = c.goal;
-  const bool track = c.kind == SampledKind::tracking;
+  const std::vector<int32_t> sch_offs = multirate_offsets(sch);
+  const int32_t* offs = multi ? sch_offs.data() : gs.ref_offset;
+  if (multi && track && out.off)
+    for (int i = 0; i < num_steps; ++i) out.off[i] = offs[i];
   if (G == 0) return I7M_OK;
   HIPCHK(hipSetDevice(h->dev));
-  const int N = (int)h->N, B = G * H;
+  const int B = G * H, n_sub = sch.total();
   const size_t T = h->T;
-  const bool admm = h->cfg.qp_mode == I7M_QP_ADMM;
   // per-run state beyond the handle's buffers: per group the state, XU_best, the scored
-  // hypothesis, goal index and alive flag; the schedules and the histories; the tracking mode's
-  // reference, phases and EE history
-  size_t bytes[TRACKING_WS_COUNT];
-  tracking_ws_bytes(G, H, N, num_steps, gs.n_endpoints, o.n_actual, noise != nullptr, gs.L, gs.ref_stride,
-                    gs.ref_phase != nullptr, bytes);
+  // hypothesis, goal index and alive flag; the schedules and the histories; the tracking kinds'
+  // reference, phases and EE history; the multi-rate kinds' controls, path and sub-step lengths
+  size_t bytes[SAMPLED_MULTIRATE_WS_COUNT];
+  sampled_call_ws_bytes(c, N, n_sub, noise != nullptr, bytes);
   // host staging, declared first: alive until the workspace's final synchronize
   const GroupStart start(h, G, H, c.xstart, gs);
   Workspace ws(h, bytes);
@@ -1873,18 +1897,20 @@ int sampled_loop(i7m_handle* h, const std::string& who, const SampledCall& c, co
          *d_fact = ws.at<double>(SWS_FACT), *d_noise = bytes[SWS_NOISE] ? ws.at<double>(SWS_NOISE) : nullptr,
          *d_dist = ws.at<double>(SWS_DIST), *d_q = ws.at<double>(SWS_Q), *d_fb = ws.at<double>(SWS_FB),
          *d_rho0 = ws.at<double>(SWS_RHO0), *d_ref = track ? ws.at<double>(TWS_REF) : nullptr,
-         *d_ee = track ? ws.at<double>(TWS_EE) : nullptr;
+         *d_ee = track ? ws.at<double>(TWS_EE) : nullptr, *d_u = ws.at<double>(SMWS_U),
+         *d_xp = ws.at<double>(SMWS_XPATH), *d_sub = ws.at<double>(SMWS_SUBDT);
   int *d_best = ws.at<int>(SWS_BEST), *d_gi = ws.at<int>(SWS_GI), *d_alive = ws.at<int>(SWS_ALIVE),
       *d_bh = ws.at<int>(SWS_BH), *d_phase = bytes[TWS_PHASE] ? ws.at<int>(TWS_PHASE) : nullptr;
   const size_t hist = history_rows(num_steps, G);
   // src/gato_mpc_batch_sample.py:111-128: goal = endpoint 0 tiled (tracking: the window at offset
   // 0), XU = [xstart, 0...], every row of a group at the group's start state, the hypotheses set
-  // on the solver
+  // on the solver; the multi-rate plant's sub-step lengths
   if ((rc = stage_start(h, start, gs, G, d_rho0, d_ref, d_phase))) return rc;
   if ((rc = loop_instances(h, start.rows, gs.endpoints, gs.n_endpoints, d_ep, d_gi, d_alive))) return rc;
   if ((rc = copy_in(h, d_xcur, c.xstart, (size_t)G * 12))) return rc;
   if ((rc = copy_in(h, d_fact, c.f_actual, 6 * (size_t)o.n_actual * G))) return rc;
   if (d_noise && (rc = copy_in(h, d_noise, noise, 3 * (size_t)num_steps * B))) return rc;
+  if (n_sub > 0 && (rc = copy_in(h, d_sub, sch.sub_dt.data(), (size_t)n_sub))) return rc;
   HIPCHK(hipMemsetAsync(d_best, 0, 4 * (size_t)G, h->stream));  // the initial solve's XU_best is row 0, :128
   if ((rc = install_wrench(h, B, c.fhyp, o.frame))) return rc;
   // the rows [lo, lo + n) (whole groups) through every MPC step on stream s, as i7m_mpc_run's
@@ -1892,12 +1918,9 @@ int sampled_loop(i7m_handle* h, const std::string& who, const SampledCall& c, co
   rc = run_ranges(h, B, [&](long lo, int n, hipStream_t s, StaggerMark* mark) -> int {
     const long glo = lo / H;
     const int ng = n / H;
-    double *xu = h->d_xu + lo * T, *out = h->d_out + lo * T, *xs = h->d_xs + lo * 12, *g = h->d_goal + lo * 3 * N;
-    // the solver state of these rows afresh, asynchronous on s (ADMM mode)
-    auto reset = [&](int what) {
-      return admm && what ? admm_reset_rows(h, lo, n, what, s, d_rho0 + lo, hipMemcpyDeviceToDevice) : I7M_OK;
-    };
-    SampledArgs a{};
+    double *xu = h->d_xu + lo * T, *xu_new = h->d_out + lo * T, *xs = h->d_xs + lo * 12, *g = h->d_goal + lo * 3 * N;
+    SampledMultirateArgs m{};  // (a single-rate kind launches with m.S alone)
+    SampledArgs& a = m.S;
     a.N = N;
     a.H = H;
     a.n_endpoints = gs.n_endpoints;
@@ -1907,7 +1930,7 @@ int sampled_loop(i7m_handle* h, const std::string& who, const SampledCall& c, co
     a.decay = o.decay;
     a.xs = xs;
     a.XU = xu;
-    a.xu_new = out;
+    a.xu_new = xu_new;
     a.goals = g;
     a.fext = h->d_fext + lo * 6;
     a.xcur = d_xcur + glo * 12;
@@ -1920,9 +1943,10 @@ int sampled_loop(i7m_handle* h, const std::string& who, const SampledCall& c, co
     a.ref_phase = d_phase ? d_phase + glo : nullptr;
     a.L = (int)gs.L;
     a.ref_stride = gs.ref_stride;
+    m.hist_stride = G;
     int rc3;
-    if ((rc3 = reset(I7M_ADMM_RESET_ALL))) return rc3;
-    if ((rc3 = run_sqp(h, n, xu, out, xs, g, 3, nullptr, lo, s, mark))) return rc3;
+    if ((rc3 = loop_reset(h, lo, n, I7M_ADMM_RESET_ALL, s, d_rho0))) return rc3;
+    if ((rc3 = run_sqp(h, n, xu, xu_new, xs, g, 3, nullptr, lo, s, mark))) return rc3;
     // launch i: select(i - 1) (i = 0: the initial solve's row 0), then plant(i) ... goal(i);
     // the last launch only selects
     for (int i = 0; i <= num_steps; ++i) {
@@ -1935,29 +1959,53 @@ int sampled_loop(i7m_handle* h, const std::string& who, const SampledCall& c, co
       a.f_actual = d_fact + ((size_t)(o.n_actual > 1 ? std::min(i, o.n_actual - 1) : 0) * G + glo) * 6;
       a.dist_out = d_dist + cur;
       a.q_out = d_q + cur * 6;
-      a.off = track && a.plant ? gs.ref_offset[i] : 0;
+      a.off = track && a.plant ? offs[i] : 0;
       a.ee_out = track ? d_ee + cur * 3 : nullptr;
-      hipLaunchKernelGGL(k_sampled_step, dim3(ng), dim3((H + 63) / 64 * 64), 0, s, h->d_model, a);
-      HIPCHK(hipGetLastError());
+      if (multi) {
+        const int s0 = a.plant ? sch.sub_start[i] : 0;
+        m.n_sub = a.plant ? sch.sub_start[i + 1] - s0 : 0;
+        m.shift = a.plant && c.shift_warm_start ? sch.shift[i] : 0;
+        m.sub_dt = d_sub + s0;
+        m.u_out = d_u + cur * 6;
+        m.xpath_out = d_xp + ((size_t)s0 * G + glo) * 6;
+        HIPCHK(i7m_launch_sampled_multirate_step(ng, H, s, h->d_model, &m));
+      } else {
+        hipLaunchKernelGGL(k_sampled_step, dim3(ng), dim3((H + 63) / 64 * 64), 0, s, h->d_model, a);
+        HIPCHK(hipGetLastError());
+      }
       if (!a.plant) break;
-      if ((rc3 = reset(o.reset_what))) return rc3;
-      if ((rc3 = run_sqp(h, n, xu, out, xs, g, 3, nullptr, lo, s))) return rc3;
+      if ((rc3 = loop_reset(h, lo, n, o.reset_what, s, d_rho0))) return rc3;
+      if ((rc3 = run_sqp(h, n, xu, xu_new, xs, g, 3, nullptr, lo, s))) return rc3;
     }
     return I7M_OK;
   }, stagger_cut_grouped(B, H));
   if (rc) return rc;
   if (num_steps > 0) {
-    if ((rc = copy_out(h, dist_out, d_dist, hist))) return rc;
-    if (q_out && (rc = copy_out(h, q_out, d_q, hist * 6))) return rc;
-    if (track && ee_out && (rc = copy_out(h, ee_out, d_ee, hist * 3))) return rc;
-    if (fbest_out && (rc = copy_out(h, fbest_out, d_fb, hist * 6))) return rc;
-    if (best_out) HIPCHK(hipMemcpyAsync(best_out, d_bh, 4 * hist, hipMemcpyDeviceToHost, h->stream));
+    if ((rc = copy_out(h, out.hist, d_dist, hist))) return rc;
+    if (out.q && (rc = copy_out(h, out.q, d_q, hist * 6))) return rc;
+    if (multi && out.u && (rc = copy_out(h, out.u, d_u, hist * 6))) return rc;
+    if (multi && out.xpath && (rc = copy_out(h, out.xpath, d_xp, (size_t)n_sub * G * 6))) return rc;
+    if (track && out.ee && (rc = copy_out(h, out.ee, d_ee, hist * 3))) return rc;
+    if (out.fbest && (rc = copy_out(h, out.fbest, d_fb, hist * 6))) return rc;
+    if (out.best) HIPCHK(hipMemcpyAsync(out.best, d_bh, 4 * hist, hipMemcpyDeviceToHost, h->stream));
   }
-  if (xcur_out && (rc = copy_out(h, xcur_out, d_xcur, (size_t)G * 12))) return rc;
-  if (xu_best_out && (rc = copy_out(h, xu_best_out, d_xub, (size_t)G * T))) return rc;
-  if (fhyp_out && (rc = copy_out(h, fhyp_out, h->d_fext, (size_t)B * 6))) return rc;
+  if (out.xcur && (rc = copy_out(h, out.xcur, d_xcur, (size_t)G * 12))) return rc;
+  if (out.xu_best && (rc = copy_out(h, out.xu_best, d_xub, (size_t)G * T))) return rc;
+  if (out.fhyp && (rc = copy_out(h, out.fhyp, h->d_fext, (size_t)B * 6))) return rc;
   return i7m_synchronize(h);
 }
+
+// A multi-rate call's options as the family's shared ones and the shift flag (null: the defaults).
+struct SharedOpts {
+  i7m_sampled_opts o;
+  int shift_warm_start = 0;
+  explicit SharedOpts(const i7m_sampled_multirate_opts* m) {
+    (void)i7m_sampled_opts_default(&o);
+    if (!m) return;
+    o = i7m_sampled_opts{m->sim_dt, m->decay, m->frame, m->reset_what, m->keep_best, m->n_actual};
+    shift_warm_start = m->shift_warm_start;
+  }
+};
 
 }  // namespace
 
@@ -1968,10 +2016,17 @@ int i7m_mpc_run_sampled(i7m_handle* h, int32_t G, int32_t H, const double* xstar
                         const double* noise, const i7m_sampled_opts* opts, double* dist_out, int32_t* best_out,
                         double* q_out, double* fbest_out, double* xcur_out, double* xu_best_out, double* fhyp_out) {
   if (!h) return fail(I7M_EINVAL, "null handle");
-  const SampledCall c = describe_call(h, SampledKind::endpoints, G, H, num_steps, opts,
+  const SampledCall c = describe_call(h, SampledKind::endpoints, G, H, num_steps, opts, 0,
                                       GoalSource::of_endpoints(endpoints, n_endpoints), xstart, fhyp, f_actual, dist_out);
-  return sampled_loop(h, "mpc_run_sampled", c, noise, dist_out, best_out, q_out, nullptr, fbest_out, xcur_out,
-                      xu_best_out, fhyp_out);
+  SampledOut out;
+  out.hist = dist_out;
+  out.best = best_out;
+  out.q = q_out;
+  out.fbest = fbest_out;
+  out.xcur = xcur_out;
+  out.xu_best = xu_best_out;
+  out.fhyp = fhyp_out;
+  return sampled_loop(h, "mpc_run_sampled", c, noise, out);
 }
 
 int i7m_mpc_run_tracking(i7m_handle* h, int32_t G, int32_t H, const double* xstart, const double* ref, int32_t L,
@@ -1980,11 +2035,19 @@ int i7m_mpc_run_tracking(i7m_handle* h, int32_t G, int32_t H, const double* xsta
                          double* err_out, int32_t* best_out, double* q_out, double* ee_out, double* fbest_out,
                          double* xcur_out, double* xu_best_out, double* fhyp_out) {
   if (!h) return fail(I7M_EINVAL, "null handle");
-  const SampledCall c = describe_call(h, SampledKind::tracking, G, H, num_steps, opts,
+  const SampledCall c = describe_call(h, SampledKind::tracking, G, H, num_steps, opts, 0,
                                       GoalSource::of_reference(ref, L, ref_stride, ref_phase, ref_offset), xstart, fhyp,
                                       f_actual, err_out);
-  return sampled_loop(h, "mpc_run_tracking", c, noise, err_out, best_out, q_out, ee_out, fbest_out, xcur_out,
-                      xu_best_out, fhyp_out);
+  SampledOut out;
+  out.hist = err_out;
+  out.best = best_out;
+  out.q = q_out;
+  out.ee = ee_out;
+  out.fbest = fbest_out;
+  out.xcur = xcur_out;
+  out.xu_best = xu_best_out;
+  out.fhyp = fhyp_out;
+  return sampled_loop(h, "mpc_run_tracking", c, noise, out);
 }
 
 int i7m_sampled_multirate_opts_default(i7m_sampled_multirate_opts* o) {
@@ -2002,171 +2065,26 @@ int i7m_sampled_multirate_opts_default(i7m_sampled_multirate_opts* o) {
   return I7M_OK;
 }
 
-}  // extern "C"
-
-namespace {
-
-// The description of a multi-rate call of the family: describe_call with the options' shared fields.
-SampledCall describe_multirate_call(const i7m_handle* h, SampledKind kind, int G, int H, int num_steps,
-                                    const i7m_sampled_multirate_opts* opts, const GoalSource& goal, const double* xstart,
-                                    const double* fhyp, const double* f_actual, const double* hist_out) {
-  i7m_sampled_multirate_opts m;
-  (void)i7m_sampled_multirate_opts_default(&m);
-  if (opts) m = *opts;
-  const i7m_sampled_opts o{m.sim_dt, m.decay, m.frame, m.reset_what, m.keep_best, m.n_actual};
-  SampledCall c = describe_call(h, kind, G, H, num_steps, &o, goal, xstart, fhyp, f_actual, hist_out);
-  c.shift_warm_start = m.shift_warm_start;
-  return c;
-}
-
-// The multi-rate sampled-wrench closed loop of both entry points (`who` names the one in the
-// messages): sampled_loop with the plant split at knot boundaries (k_sampled_multirate_step) and,
-// in tracking mode, the window's schedule computed here (the knots completed so far).
-int sampled_multirate_loop(i7m_handle* h, const std::string& who, const SampledCall& c, const double* noise,
-                           double* dist_out, int32_t* best_out, double* q_out, double* u_out, double* xpath_out,
-                           double* ee_out, int32_t* off_out, double* fbest_out, double* xcur_out, double* xu_best_out,
-                           double* fhyp_out) {
-  if (h->ctrl.open) return session_open();
-  const int N = (int)h->N;
-  MultirateSchedule sch;
-  {
-    const char* which = "";
-    long at = 0;
-    if (!sampled_multirate_call_ok(c, N, &sch, &which, &at))
-      return fail(I7M_EINVAL, sampled_multirate_refusal(who, which, at, c, N));
-  }
-  const int G = c.G, H = c.H, num_steps = c.num_steps;
-  const i7m_sampled_opts& o = c.o;
-  const GoalSource& gs = c.goal;
-  const bool track = c.kind == SampledKind::tracking_multirate;
-  const std::vector<int32_t> offs = multirate_offsets(sch);
-  if (track && off_out)
-    for (int i = 0; i < num_steps; ++i) off_out[i] = offs[i];
-  if (G == 0) return I7M_OK;
-  int rc;
-  HIPCHK(hipSetDevice(h->dev));
-  const int B = G * H, n_sub = sch.total();
-  const size_t T = h->T;
-  const bool admm = h->cfg.qp_mode == I7M_QP_ADMM;
-  size_t bytes[SAMPLED_MULTIRATE_WS_COUNT];
-  sampled_multirate_ws_bytes(G, H, N, num_steps, n_sub, gs.n_endpoints, o.n_actual, noise != nullptr, gs.L, gs.ref_stride,
-                             gs.ref_phase != nullptr, bytes);
-  // host staging, declared first: alive until the workspace's final synchronize
-  const GroupStart start(h, G, H, c.xstart, gs);
-  Workspace ws(h, bytes);
-  if (!ws.base) return fail(I7M_ENOMEM, who + ": device allocation failed");
-  double *d_ep = ws.at<double>(SWS_EP), *d_xcur = ws.at<double>(SWS_XCUR), *d_xub = ws.at<double>(SWS_XUB),
-         *d_fact = ws.at<double>(SWS_FACT), *d_noise = bytes[SWS_NOISE] ? ws.at<double>(SWS_NOISE) : nullptr,
-         *d_dist = ws.at<double>(SWS_DIST), *d_q = ws.at<double>(SWS_Q), *d_fb = ws.at<double>(SWS_FB),
-         *d_rho0 = ws.at<double>(SWS_RHO0), *d_ref = track ? ws.at<double>(TWS_REF) : nullptr,
-         *d_ee = track ? ws.at<double>(TWS_EE) : nullptr, *d_u = ws.at<double>(SMWS_U),
-         *d_xp = ws.at<double>(SMWS_XPATH), *d_sub = ws.at<double>(SMWS_SUBDT);
-  int *d_best = ws.at<int>(SWS_BEST), *d_gi = ws.at<int>(SWS_GI), *d_alive = ws.at<int>(SWS_ALIVE),
-      *d_bh = ws.at<int>(SWS_BH), *d_phase = bytes[TWS_PHASE] ? ws.at<int>(TWS_PHASE) : nullptr;
-  const size_t hist = history_rows(num_steps, G);
-  // the start of i7m_mpc_run_sampled / _tracking, and the sub-step lengths
-  if ((rc = stage_start(h, start, gs, G, d_rho0, d_ref, d_phase))) return rc;
-  if ((rc = loop_instances(h, start.rows, gs.endpoints, gs.n_endpoints, d_ep, d_gi, d_alive))) return rc;
-  if ((rc = copy_in(h, d_xcur, c.xstart, (size_t)G * 12))) return rc;
-  if ((rc = copy_in(h, d_fact, c.f_actual, 6 * (size_t)o.n_actual * G))) return rc;
-  if (d_noise && (rc = copy_in(h, d_noise, noise, 3 * (size_t)num_steps * B))) return rc;
-  if (n_sub > 0 && (rc = copy_in(h, d_sub, sch.sub_dt.data(), (size_t)n_sub))) return rc;
-  HIPCHK(hipMemsetAsync(d_best, 0, 4 * (size_t)G, h->stream));  // the initial solve's XU_best is row 0
-  if ((rc = install_wrench(h, B, c.fhyp, o.frame))) return rc;
-  // the rows [lo, lo + n) (whole groups) through every MPC step on stream s, as sampled_loop's ranges
-  rc = run_ranges(h, B, [&](long lo, int n, hipStream_t s, StaggerMark* mark) -> int {
-    const long glo = lo / H;
-    const int ng = n / H;
-    double *xu = h->d_xu + lo * T, *out = h->d_out + lo * T, *xs = h->d_xs + lo * 12, *g = h->d_goal + lo * 3 * N;
-    auto reset = [&](int what) {
-      return admm && what ? admm_reset_rows(h, lo, n, what, s, d_rho0 + lo, hipMemcpyDeviceToDevice) : I7M_OK;
-    };
-    SampledMultirateArgs m{};
-    SampledArgs& a = m.S;
-    a.N = N;
-    a.H = H;
-    a.n_endpoints = gs.n_endpoints;
-    a.frame_world = o.frame == I7M_WRENCH_WORLD;
-    a.keep_best = o.keep_best != 0;
-    a.sim_dt = o.sim_dt;
-    a.decay = o.decay;
-    a.xs = xs;
-    a.XU = xu;
-    a.xu_new = out;
-    a.goals = g;
-    a.fext = h->d_fext + lo * 6;
-    a.xcur = d_xcur + glo * 12;
-    a.xub = d_xub + glo * T;
-    a.best = d_best + glo;
-    a.goal_idx = d_gi + glo;
-    a.alive = d_alive + glo;
-    a.endpoints = track ? nullptr : d_ep;
-    a.ref = d_ref;
-    a.ref_phase = d_phase ? d_phase + glo : nullptr;
-    a.L = (int)gs.L;
-    a.ref_stride = gs.ref_stride;
-    m.hist_stride = G;
-    int rc3;
-    if ((rc3 = reset(I7M_ADMM_RESET_ALL))) return rc3;
-    if ((rc3 = run_sqp(h, n, xu, out, xs, g, 3, nullptr, lo, s, mark))) return rc3;
-    // launch i: select(i - 1) (i = 0: the initial solve's row 0), then plant(i) ... goal(i);
-    // the last launch only selects
-    for (int i = 0; i <= num_steps; ++i) {
-      a.select = i == 0 ? 2 : 1;
-      a.plant = i < num_steps;
-      const size_t rec = ((size_t)std::max(i - 1, 0)) * G + glo, cur = (size_t)std::min(i, std::max(num_steps - 1, 0)) * G + glo;
-      a.noise = d_noise && i > 0 ? d_noise + ((size_t)(i - 1) * B + lo) * 3 : nullptr;
-      a.best_out = d_bh + rec;
-      a.fbest_out = d_fb + rec * 6;
-      a.f_actual = d_fact + ((size_t)(o.n_actual > 1 ? std::min(i, o.n_actual - 1) : 0) * G + glo) * 6;
-      a.dist_out = d_dist + cur;
-      a.q_out = d_q + cur * 6;
-      a.off = track && a.plant ? offs[i] : 0;
-      a.ee_out = track ? d_ee + cur * 3 : nullptr;
-      const int s0 = a.plant ? sch.sub_start[i] : 0;
-      m.n_sub = a.plant ? sch.sub_start[i + 1] - s0 : 0;
-      m.shift = a.plant && c.shift_warm_start ? sch.shift[i] : 0;
-      m.sub_dt = d_sub + s0;
-      m.u_out = d_u + cur * 6;
-      m.xpath_out = d_xp + ((size_t)s0 * G + glo) * 6;
-      HIPCHK(i7m_launch_sampled_multirate_step(ng, H, s, h->d_model, &m));
-      if (!a.plant) break;
-      if ((rc3 = reset(o.reset_what))) return rc3;
-      if ((rc3 = run_sqp(h, n, xu, out, xs, g, 3, nullptr, lo, s))) return rc3;
-    }
-    return I7M_OK;
-  }, stagger_cut_grouped(B, H));
-  if (rc) return rc;
-  if (num_steps > 0) {
-    if ((rc = copy_out(h, dist_out, d_dist, hist))) return rc;
-    if (q_out && (rc = copy_out(h, q_out, d_q, hist * 6))) return rc;
-    if (u_out && (rc = copy_out(h, u_out, d_u, hist * 6))) return rc;
-    if (xpath_out && (rc = copy_out(h, xpath_out, d_xp, (size_t)n_sub * G * 6))) return rc;
-    if (track && ee_out && (rc = copy_out(h, ee_out, d_ee, hist * 3))) return rc;
-    if (fbest_out && (rc = copy_out(h, fbest_out, d_fb, hist * 6))) return rc;
-    if (best_out) HIPCHK(hipMemcpyAsync(best_out, d_bh, 4 * hist, hipMemcpyDeviceToHost, h->stream));
-  }
-  if (xcur_out && (rc = copy_out(h, xcur_out, d_xcur, (size_t)G * 12))) return rc;
-  if (xu_best_out && (rc = copy_out(h, xu_best_out, d_xub, (size_t)G * T))) return rc;
-  if (fhyp_out && (rc = copy_out(h, fhyp_out, h->d_fext, (size_t)B * 6))) return rc;
-  return i7m_synchronize(h);
-}
-
-}  // namespace
-
-extern "C" {
-
 int i7m_mpc_run_sampled_multirate(i7m_handle* h, int32_t G, int32_t H, const double* xstart, const double* endpoints,
                                   int32_t n_endpoints, int32_t num_steps, const double* fhyp, const double* f_actual,
                                   const double* noise, const i7m_sampled_multirate_opts* opts, double* dist_out,
                                   int32_t* best_out, double* q_out, double* u_out, double* xpath_out, double* fbest_out,
                                   double* xcur_out, double* xu_best_out, double* fhyp_out) {
   if (!h) return fail(I7M_EINVAL, "null handle");
-  const SampledCall c = describe_multirate_call(h, SampledKind::endpoints_multirate, G, H, num_steps, opts,
-                                                GoalSource::of_endpoints(endpoints, n_endpoints), xstart, fhyp, f_actual,
-                                                dist_out);
-  return sampled_multirate_loop(h, "mpc_run_sampled_multirate", c, noise, dist_out, best_out, q_out, u_out, xpath_out,
-                                nullptr, nullptr, fbest_out, xcur_out, xu_best_out, fhyp_out);
+  const SharedOpts so(opts);
+  const SampledCall c = describe_call(h, SampledKind::endpoints_multirate, G, H, num_steps, &so.o, so.shift_warm_start,
+                                      GoalSource::of_endpoints(endpoints, n_endpoints), xstart, fhyp, f_actual, dist_out);
+  SampledOut out;
+  out.hist = dist_out;
+  out.best = best_out;
+  out.q = q_out;
+  out.u = u_out;
+  out.xpath = xpath_out;
+  out.fbest = fbest_out;
+  out.xcur = xcur_out;
+  out.xu_best = xu_best_out;
+  out.fhyp = fhyp_out;
+  return sampled_loop(h, "mpc_run_sampled_multirate", c, noise, out);
 }
 
 int i7m_mpc_run_tracking_multirate(i7m_handle* h, int32_t G, int32_t H, const double* xstart, const double* ref,
@@ -2176,11 +2094,23 @@ int i7m_mpc_run_tracking_multirate(i7m_handle* h, int32_t G, int32_t H, const do
                                    double* q_out, double* u_out, double* xpath_out, double* ee_out, int32_t* off_out,
                                    double* fbest_out, double* xcur_out, double* xu_best_out, double* fhyp_out) {
   if (!h) return fail(I7M_EINVAL, "null handle");
-  const SampledCall c = describe_multirate_call(h, SampledKind::tracking_multirate, G, H, num_steps, opts,
-                                                GoalSource::of_reference(ref, L, ref_stride, ref_phase, nullptr), xstart,
-                                                fhyp, f_actual, err_out);
-  return sampled_multirate_loop(h, "mpc_run_tracking_multirate", c, noise, err_out, best_out, q_out, u_out, xpath_out,
-                                ee_out, off_out, fbest_out, xcur_out, xu_best_out, fhyp_out);
+  const SharedOpts so(opts);
+  const SampledCall c = describe_call(h, SampledKind::tracking_multirate, G, H, num_steps, &so.o, so.shift_warm_start,
+                                      GoalSource::of_reference(ref, L, ref_stride, ref_phase, nullptr), xstart, fhyp,
+                                      f_actual, err_out);
+  SampledOut out;
+  out.hist = err_out;
+  out.best = best_out;
+  out.q = q_out;
+  out.u = u_out;
+  out.xpath = xpath_out;
+  out.ee = ee_out;
+  out.off = off_out;
+  out.fbest = fbest_out;
+  out.xcur = xcur_out;
+  out.xu_best = xu_best_out;
+  out.fhyp = fhyp_out;
+  return sampled_loop(h, "mpc_run_tracking_multirate", c, noise, out);
 }
 
 }  // extern "C"
@@ -2192,10 +2122,8 @@ namespace {
 int ctrl_solve(i7m_handle* h, int what) {
   const CtrlSession& c = h->ctrl;
   const int B = c.G * c.H;
-  int rc;
-  if (h->cfg.qp_mode == I7M_QP_ADMM && what &&
-      (rc = admm_reset_rows(h, 0, B, what, h->stream, c.dev.at<double>(CWS_RHO0), hipMemcpyDeviceToDevice)))
-    return rc;
+  const int rc = loop_reset(h, 0, B, what, h->stream, c.dev.at<double>(CWS_RHO0));
+  if (rc) return rc;
   return run_sqp(h, B, h->d_xu, h->d_out, h->d_xs, h->d_goal, 3, nullptr);
 }
 
@@ -2213,11 +2141,11 @@ int i7m_ctrl_begin(i7m_handle* h, int32_t G, int32_t H, const double* x0, const 
   const std::string who = "ctrl_begin";
   if (!h) return fail(I7M_EINVAL, "null handle");
   if (h->ctrl.open) return fail(I7M_EINVAL, who + ": a controller session is already open on this handle");
-  const SampledCall call = describe_call(h, SampledKind::session, G, H, 0, opts,
+  const SampledCall call = describe_call(h, SampledKind::session, G, H, 0, opts, 0,
                                          GoalSource::of_reference(ref, L, ref_stride, ref_phase, nullptr), x0, fhyp, nullptr,
                                          nullptr);
   int rc;
-  if ((rc = check_call(who, call))) return rc;
+  if ((rc = check_call(who, call, (int)h->N, nullptr))) return rc;
   const i7m_sampled_opts& o = call.o;
   HIPCHK(hipSetDevice(h->dev));
   HIPCHK(hipStreamSynchronize(h->stream));

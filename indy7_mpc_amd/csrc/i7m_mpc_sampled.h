@@ -186,6 +186,17 @@ __device__ __forceinline__ void spread_rows(double* XU, double* xs, const double
   for (int e = l; e < 12 * H; e += nt) xs[e] = s_x[e % 12];
 }
 
+// spread_rows with the warm start shifted by sh = 18 s entries (s knots completed, the multi-rate
+// loops' shift_warm_start): XU[e] = XU_best[e + sh] for 12 <= e < T - sh, the tail keeps XU_best[e]
+__device__ __forceinline__ void spread_rows_shifted(double* XU, double* xs, const double* xub, const double* s_x, int H,
+                                                    int T, int sh, int l, int nt) {
+  for (int e = l; e < T; e += nt) {
+    const double v = e < 12 ? s_x[e] : (e < T - sh ? xub[e + sh] : xub[e]);
+    for (int hh = 0; hh < H; ++hh) XU[(long)hh * T + e] = v;
+  }
+  for (int e = l; e < 12 * H; e += nt) xs[e] = s_x[e % 12];
+}
+
 // the window: one load per column (knot e / 3, coordinate e % 3) and H stores
 __device__ __forceinline__ void window_rows(double* goals, const double* ref, long ph, long off, int L, int ref_stride,
                                             int N, int H, int l, int nt) {
@@ -195,42 +206,112 @@ __device__ __forceinline__ void window_rows(double* goals, const double* ref, lo
   }
 }
 
+// ---- the pieces k_sampled_step and k_sampled_multirate_step (i7m_mpc_sampled_multirate.h) share:
+// all but the plant and score pass between sampled_select and sampled_finish.  g the group, r0 its
+// first row, xub its XU_best, track / ph the launch's goal source and the group's phase: loaded once
+// by the kernel and passed in -------------------------------------------------------------------------
+
+// a stopped group's records: NaN / -1 from the step after its stop on (the kernel then returns)
+__device__ __forceinline__ void sampled_stopped(const SampledArgs& A, int g, int l) {
+  const double nan = __builtin_nan("");
+  if (A.select == 1) {
+    if (A.best_out && l == 0) A.best_out[g] = -1;
+    if (A.fbest_out && l < 6) A.fbest_out[6L * g + l] = nan;
+  }
+  if (A.plant) {
+    if (l == 0) A.dist_out[g] = nan;
+    if (A.q_out && l < 6) A.q_out[6L * g + l] = nan;
+  }
+}
+
+// select(i - 1): select_resample of the scored row, recorded with its wrench, and the barrier
+// before the plant and the score read XU_best and the resampled rows
+__device__ __forceinline__ void sampled_select(const SampledArgs& A, int g, int l, int nt, long r0, double* xub) {
+  if (!A.select) return;
+  const int H = A.H, T = 18 * A.N - 6;
+  const int b = A.best[g];
+  double fb[6];
+  select_resample(xub, A.xu_new + r0 * T, A.fext + r0 * 6, A.noise ? A.noise + r0 * 3 : nullptr, b, H, T, l, nt,
+                  A.select == 1, A.keep_best != 0, A.decay, fb);
+  if (A.select == 1 && l == 0) {
+    if (A.best_out) A.best_out[g] = b;
+    if (A.fbest_out)
+#pragma unroll
+      for (int k = 0; k < 6; ++k) A.fbest_out[6L * g + k] = fb[k];
+  }
+  __syncthreads();  // XU_best and the resampled rows are the plant's and the score's inputs
+}
+
+// The step after the plant and the score (every lane holds the new state xn, lane l its error err):
+// the group's argmin into best[g]; the goal distance of the new state, the endpoint switch or the
+// stop; xcur / q_out; the spread (warm start shifted by sh entries, 0: none); the window or the new
+// endpoint re-tiled.
+__device__ __forceinline__ void sampled_finish(const DevModel& M, const SampledArgs& A, int g, int l, int nt, long r0,
+                                               const double* xub, bool track, long ph, int sh, double err,
+                                               const double xn[12]) {
+  __shared__ double s_x[12], s_err[4];
+  __shared__ int s_idx[4], s_switch;
+  const int H = A.H, N = A.N, T = 18 * N - 6;
+  int idx;
+  group_argmin_park(err, idx, l, H, s_err, s_idx);
+  if (l == 0) {
+#pragma unroll
+    for (int k = 0; k < 12; ++k) s_x[k] = xn[k];
+  }
+  __syncthreads();
+  if (l == 0) {
+    A.best[g] = group_argmin_merge(err, idx, nt, H, s_err, s_idx);
+    // the goal of the new state (src/gato_mpc_batch_sample.py:203-217), or the window's first point
+    double c[6], s[6], p[3];
+    sincos6(xn, c, s);
+    fk_pos(M, c, s, p);
+    const double* gl = track ? A.ref + track_index(ph, A.off, 0, A.L) * A.ref_stride : A.goals + r0 * 3 * N;
+    const double e0 = p[0] - gl[0], e1 = p[1] - gl[1], e2 = p[2] - gl[2];
+    const double d = sqrt(e0 * e0 + e1 * e1 + e2 * e2);
+    A.dist_out[g] = d;
+    if (A.ee_out)
+#pragma unroll
+      for (int k = 0; k < 3; ++k) A.ee_out[3L * g + k] = p[k];
+    int sw = -1;
+    if (!track && d < SAMPLED_GOAL_RADIUS) {
+      if (A.goal_idx[g] < A.n_endpoints - 1) {
+        sw = A.goal_idx[g] + 1;
+        A.goal_idx[g] = sw;
+      } else {
+        A.alive[g] = 0;
+      }
+    }
+    s_switch = sw;
+  }
+  if (l < 12) A.xcur[12L * g + l] = s_x[l];
+  if (A.q_out && l < 6) A.q_out[6L * g + l] = s_x[l];
+  if (sh > 0)
+    spread_rows_shifted(A.XU + r0 * T, A.xs + r0 * 12, xub, s_x, H, T, sh, l, nt);
+  else
+    spread_rows(A.XU + r0 * T, A.xs + r0 * 12, xub, s_x, H, T, l, nt);
+  __syncthreads();
+  const int sw = s_switch;
+  if (track) {
+    window_rows(A.goals + r0 * 3 * N, A.ref, ph, A.off, A.L, A.ref_stride, N, H, l, nt);
+  } else if (sw >= 0) {
+    double* gl = A.goals + r0 * 3 * N;
+    for (int e = l; e < 3 * N * H; e += nt) gl[e] = A.endpoints[3 * sw + e % 3];
+  }
+}
+
 // One workgroup per group, one lane per hypothesis (H lanes rounded up to whole waves, <= 4 waves).
 __global__ void __launch_bounds__(256) k_sampled_step(const DevModel* __restrict__ Mg, const SampledArgs A) {
   const int g = blockIdx.x, l = threadIdx.x, nt = blockDim.x;
-  const int H = A.H, N = A.N, T = 18 * N - 6;
-  const double nan = __builtin_nan("");
-  if (!A.alive[g]) {  // a stopped group: NaN / -1 from the step after its stop on
-    if (A.select == 1) {
-      if (A.best_out && l == 0) A.best_out[g] = -1;
-      if (A.fbest_out && l < 6) A.fbest_out[6L * g + l] = nan;
-    }
-    if (A.plant) {
-      if (l == 0) A.dist_out[g] = nan;
-      if (A.q_out && l < 6) A.q_out[6L * g + l] = nan;
-    }
+  const int H = A.H, T = 18 * A.N - 6;
+  if (!A.alive[g]) {
+    sampled_stopped(A, g, l);
     return;
   }
-  __shared__ double s_x[12], s_err[4];
-  __shared__ int s_idx[4], s_switch;
   const long r0 = (long)g * H;
   double* xub = A.xub + (long)g * T;
   const bool track = A.ref != nullptr;  // wave-uniform: the goal source of the launch
   const long ph = track && A.ref_phase ? A.ref_phase[g] : 0;
-
-  if (A.select) {
-    const int b = A.best[g];
-    double fb[6];
-    select_resample(xub, A.xu_new + r0 * T, A.fext + r0 * 6, A.noise ? A.noise + r0 * 3 : nullptr, b, H, T, l, nt,
-                    A.select == 1, A.keep_best != 0, A.decay, fb);
-    if (A.select == 1 && l == 0) {
-      if (A.best_out) A.best_out[g] = b;
-      if (A.fbest_out)
-#pragma unroll
-        for (int k = 0; k < 6; ++k) A.fbest_out[6L * g + k] = fb[k];
-    }
-    __syncthreads();  // XU_best and the resampled rows are the plant's and the score's inputs
-  }
+  sampled_select(A, g, l, nt, r0, xub);
   if (!A.plant) return;
 
   double xl[12], u[6], xn[12], err = 0.0;
@@ -256,48 +337,7 @@ __global__ void __launch_bounds__(256) k_sampled_step(const DevModel* __restrict
       err = state_err(qo, vo, xn);
     }
   }
-  int idx;
-  group_argmin_park(err, idx, l, H, s_err, s_idx);
-  if (l == 0) {
-#pragma unroll
-    for (int k = 0; k < 12; ++k) s_x[k] = xn[k];
-  }
-  __syncthreads();
-  if (l == 0) {
-    A.best[g] = group_argmin_merge(err, idx, nt, H, s_err, s_idx);
-    // the goal of the new state (src/gato_mpc_batch_sample.py:203-217), or the window's first point
-    double c[6], s[6], p[3];
-    sincos6(xn, c, s);
-    fk_pos(*Mg, c, s, p);
-    const double* gl = track ? A.ref + track_index(ph, A.off, 0, A.L) * A.ref_stride : A.goals + r0 * 3 * N;
-    const double e0 = p[0] - gl[0], e1 = p[1] - gl[1], e2 = p[2] - gl[2];
-    const double d = sqrt(e0 * e0 + e1 * e1 + e2 * e2);
-    A.dist_out[g] = d;
-    if (A.ee_out)
-#pragma unroll
-      for (int k = 0; k < 3; ++k) A.ee_out[3L * g + k] = p[k];
-    int sw = -1;
-    if (!track && d < SAMPLED_GOAL_RADIUS) {
-      if (A.goal_idx[g] < A.n_endpoints - 1) {
-        sw = A.goal_idx[g] + 1;
-        A.goal_idx[g] = sw;
-      } else {
-        A.alive[g] = 0;
-      }
-    }
-    s_switch = sw;
-  }
-  if (l < 12) A.xcur[12L * g + l] = s_x[l];
-  if (A.q_out && l < 6) A.q_out[6L * g + l] = s_x[l];
-  spread_rows(A.XU + r0 * T, A.xs + r0 * 12, xub, s_x, H, T, l, nt);
-  __syncthreads();
-  const int sw = s_switch;
-  if (track) {
-    window_rows(A.goals + r0 * 3 * N, A.ref, ph, A.off, A.L, A.ref_stride, N, H, l, nt);
-  } else if (sw >= 0) {
-    double* gl = A.goals + r0 * 3 * N;
-    for (int e = l; e < 3 * N * H; e += nt) gl[e] = A.endpoints[3 * sw + e % 3];
-  }
+  sampled_finish(*Mg, A, g, l, nt, r0, xub, track, ph, 0, err, xn);
 }
 
 }  // namespace i7m

@@ -50,61 +50,28 @@ struct SampledMultirateArgs {
 
 #ifdef I7M_SAMPLED_MULTIRATE_KERNEL  // (i7m_mpc_sampled_multirate_tu.hip: the kernel lives in that unit alone)
 
-// spread_rows with the warm start shifted by sh = 18 s entries: XU[e] = XU_best[e + sh] for
-// 12 <= e < T - sh, the tail keeps XU_best[e]
-__device__ __forceinline__ void spread_rows_shifted(double* XU, double* xs, const double* xub, const double* s_x, int H,
-                                                    int T, int sh, int l, int nt) {
-  for (int e = l; e < T; e += nt) {
-    const double v = e < 12 ? s_x[e] : (e < T - sh ? xub[e + sh] : xub[e]);
-    for (int hh = 0; hh < H; ++hh) XU[(long)hh * T + e] = v;
-  }
-  for (int e = l; e < 12 * H; e += nt) xs[e] = s_x[e % 12];
-}
-
 // One workgroup per group, one lane per hypothesis (H lanes rounded up to whole waves, <= 4 waves).
 __global__ void __launch_bounds__(256) k_sampled_multirate_step(const DevModel* __restrict__ Mg,
                                                                 const SampledMultirateArgs M) {
   const SampledArgs& A = M.S;
   const int g = blockIdx.x, l = threadIdx.x, nt = blockDim.x;
-  const int H = A.H, N = A.N, T = 18 * N - 6;
+  const int H = A.H, T = 18 * A.N - 6;
   const int ns = M.n_sub < MULTIRATE_MAX_SUB ? M.n_sub : MULTIRATE_MAX_SUB;  // the loops' bound
-  const double nan = __builtin_nan("");
-  if (!A.alive[g]) {  // a stopped group: NaN / -1 from the step after its stop on
-    if (A.select == 1) {
-      if (A.best_out && l == 0) A.best_out[g] = -1;
-      if (A.fbest_out && l < 6) A.fbest_out[6L * g + l] = nan;
-    }
-    if (A.plant) {
-      if (l == 0) A.dist_out[g] = nan;
-      if (l < 6) {
-        if (A.q_out) A.q_out[6L * g + l] = nan;
-        M.u_out[6L * g + l] = nan;
-        if (M.xpath_out)
-          for (int s = 0; s < ns; ++s) M.xpath_out[((long)s * M.hist_stride + g) * 6 + l] = nan;
-      }
+  if (!A.alive[g]) {  // a stopped group: its u and path are NaN too
+    sampled_stopped(A, g, l);
+    if (A.plant && l < 6) {
+      const double nan = __builtin_nan("");
+      M.u_out[6L * g + l] = nan;
+      if (M.xpath_out)
+        for (int s = 0; s < ns; ++s) M.xpath_out[((long)s * M.hist_stride + g) * 6 + l] = nan;
     }
     return;
   }
-  __shared__ double s_x[12], s_err[4];
-  __shared__ int s_idx[4], s_switch;
   const long r0 = (long)g * H;
   double* xub = A.xub + (long)g * T;
   const bool track = A.ref != nullptr;  // wave-uniform: the goal source of the launch
   const long ph = track && A.ref_phase ? A.ref_phase[g] : 0;
-
-  if (A.select) {
-    const int b = A.best[g];
-    double fb[6];
-    select_resample(xub, A.xu_new + r0 * T, A.fext + r0 * 6, A.noise ? A.noise + r0 * 3 : nullptr, b, H, T, l, nt,
-                    A.select == 1, A.keep_best != 0, A.decay, fb);
-    if (A.select == 1 && l == 0) {
-      if (A.best_out) A.best_out[g] = b;
-      if (A.fbest_out)
-#pragma unroll
-        for (int k = 0; k < 6; ++k) A.fbest_out[6L * g + k] = fb[k];
-    }
-    __syncthreads();  // XU_best and the resampled rows are the plant's and the score's inputs
-  }
+  sampled_select(A, g, l, nt, r0, xub);
   if (!A.plant) return;
 
   double xl[12], u[6], xn[12], err = 0.0;
@@ -165,52 +132,7 @@ __global__ void __launch_bounds__(256) k_sampled_multirate_step(const DevModel* 
       }
     }
   }
-  int idx;
-  group_argmin_park(err, idx, l, H, s_err, s_idx);
-  if (l == 0) {
-#pragma unroll
-    for (int k = 0; k < 12; ++k) s_x[k] = xn[k];
-  }
-  __syncthreads();
-  if (l == 0) {
-    A.best[g] = group_argmin_merge(err, idx, nt, H, s_err, s_idx);
-    // the goal of the new state (src/gato_mpc_batch_sample.py:203-217), or the window's first point
-    double c[6], s[6], p[3];
-    sincos6(xn, c, s);
-    fk_pos(*Mg, c, s, p);
-    const double* gl = track ? A.ref + track_index(ph, A.off, 0, A.L) * A.ref_stride : A.goals + r0 * 3 * N;
-    const double e0 = p[0] - gl[0], e1 = p[1] - gl[1], e2 = p[2] - gl[2];
-    const double d = sqrt(e0 * e0 + e1 * e1 + e2 * e2);
-    A.dist_out[g] = d;
-    if (A.ee_out)
-#pragma unroll
-      for (int k = 0; k < 3; ++k) A.ee_out[3L * g + k] = p[k];
-    int sw = -1;
-    if (!track && d < SAMPLED_GOAL_RADIUS) {
-      if (A.goal_idx[g] < A.n_endpoints - 1) {
-        sw = A.goal_idx[g] + 1;
-        A.goal_idx[g] = sw;
-      } else {
-        A.alive[g] = 0;
-      }
-    }
-    s_switch = sw;
-  }
-  if (l < 12) A.xcur[12L * g + l] = s_x[l];
-  if (A.q_out && l < 6) A.q_out[6L * g + l] = s_x[l];
-  const int sh = 18 * M.shift;
-  if (sh > 0)
-    spread_rows_shifted(A.XU + r0 * T, A.xs + r0 * 12, xub, s_x, H, T, sh, l, nt);
-  else
-    spread_rows(A.XU + r0 * T, A.xs + r0 * 12, xub, s_x, H, T, l, nt);
-  __syncthreads();
-  const int sw = s_switch;
-  if (track) {
-    window_rows(A.goals + r0 * 3 * N, A.ref, ph, A.off, A.L, A.ref_stride, N, H, l, nt);
-  } else if (sw >= 0) {
-    double* gl = A.goals + r0 * 3 * N;
-    for (int e = l; e < 3 * N * H; e += nt) gl[e] = A.endpoints[3 * sw + e % 3];
-  }
+  sampled_finish(*Mg, A, g, l, nt, r0, xub, track, ph, 18 * M.shift, err, xn);
 }
 
 #endif  // I7M_SAMPLED_MULTIRATE_KERNEL

@@ -461,6 +461,10 @@ struct GoalSource {
 // finite and > 0 but not bounded by dt, shift_warm_start is 0 or 1, and the tracking window's
 // schedule is the library's (the knots completed), so no ref_offset is asked for.
 enum class SampledKind { endpoints, tracking, session, endpoints_multirate, tracking_multirate };
+inline bool multirate_kind(SampledKind k) {
+  return k == SampledKind::endpoints_multirate || k == SampledKind::tracking_multirate;
+}
+inline bool tracking_kind(SampledKind k) { return k != SampledKind::endpoints && k != SampledKind::endpoints_multirate; }
 struct SampledCall {
   SampledKind kind = SampledKind::endpoints;
   int qp_mode = I7M_QP_DIRECT, max_batch = 0;
@@ -482,9 +486,7 @@ inline bool sampled_call_ok(const SampledCall& c, const char** which, long* at) 
     *at = a;
     return false;
   };
-  const bool multi = c.kind == SampledKind::endpoints_multirate || c.kind == SampledKind::tracking_multirate;
-  const bool loop = c.kind != SampledKind::session;
-  const bool track = c.kind != SampledKind::endpoints && c.kind != SampledKind::endpoints_multirate;
+  const bool multi = multirate_kind(c.kind), loop = c.kind != SampledKind::session, track = tracking_kind(c.kind);
   const GoalSource& g = c.goal;
   if (c.qp_mode != I7M_QP_DIRECT && c.qp_mode != I7M_QP_ADMM) return no("qp_mode", c.qp_mode);
   if (c.H < 1 || c.H > 256 || (c.H & (c.H - 1))) return no("H", c.H);
@@ -537,7 +539,7 @@ inline std::string sampled_refusal(const std::string& who, const std::string& wh
 // step).  On success *sch is the schedule the loop runs.
 inline bool sampled_multirate_call_ok(const SampledCall& c, int N, MultirateSchedule* sch, const char** which, long* at) {
   *sch = MultirateSchedule{};
-  if (c.kind != SampledKind::endpoints_multirate && c.kind != SampledKind::tracking_multirate) {
+  if (!multirate_kind(c.kind)) {
     *which = "kind";
     *at = (long)c.kind;
     return false;
@@ -571,6 +573,22 @@ inline void sampled_multirate_ws_bytes(int G, int H, int N, int num_steps, int n
   bytes[SMWS_U] = 6 * 8 * history_rows(num_steps, G);
   bytes[SMWS_XPATH] = 6 * 8 * history_rows(n_sub, G);
   bytes[SMWS_SUBDT] = 8 * (size_t)std::max(n_sub, 1);
+}
+// The one request of a loop of the family, whichever its kind: a multi-rate call's is
+// sampled_multirate_ws_bytes with its schedule's n_sub sub-steps; a single-rate call's is
+// tracking_ws_bytes, the three multi-rate sub-buffers empty, so they take no room and its allocation
+// is what it was.
+inline void sampled_call_ws_bytes(const SampledCall& c, int N, int n_sub, bool noise,
+                                  size_t bytes[SAMPLED_MULTIRATE_WS_COUNT]) {
+  const GoalSource& g = c.goal;
+  if (multirate_kind(c.kind)) {
+    sampled_multirate_ws_bytes(c.G, c.H, N, c.num_steps, n_sub, g.n_endpoints, c.o.n_actual, noise, g.L, g.ref_stride,
+                               g.ref_phase != nullptr, bytes);
+    return;
+  }
+  tracking_ws_bytes(c.G, c.H, N, c.num_steps, g.n_endpoints, c.o.n_actual, noise, g.L, g.ref_stride,
+                    g.ref_phase != nullptr, bytes);
+  bytes[SMWS_U] = bytes[SMWS_XPATH] = bytes[SMWS_SUBDT] = 0;
 }
 
 // i7m_ctrl_step's: the pointers, the clock, the offset, and a host scan of the measurement (a real

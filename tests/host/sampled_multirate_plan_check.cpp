@@ -1,7 +1,7 @@
 // Host check of the multi-rate sampled-wrench loops' plan (indy7_mpc_amd/csrc/i7m_plan.h):
 // sampled_multirate_call_ok and its texts (everything the family's check refuses but sim_dt > dt,
 // the schedule's refusals, shift_warm_start), sampled_call_ok unchanged for the single-rate kinds,
-// multirate_offsets, and sampled_multirate_ws_bytes.
+// multirate_offsets, sampled_multirate_ws_bytes, and the loops' one request, sampled_call_ws_bytes.
 #include <cstdio>
 #include <limits>
 
@@ -223,6 +223,51 @@ int main() {
     }
     sampled_multirate_ws_bytes(3, 2, 8, 0, 0, 1, 1, false, 0, 0, false, by);  // no steps: one row of each
     CHECK(by[SMWS_U] == 144 && by[SMWS_XPATH] == 144 && by[SMWS_SUBDT] == 8 && by[TWS_REF] == 0);
+  }
+
+  // the loops' one request (sampled_call_ws_bytes): a single-rate kind's offsets and total are
+  // tracking_ws_bytes', a multi-rate kind's sampled_multirate_ws_bytes'; without noise, phases or a
+  // reference those sub-buffers take no room, and a single-rate call's multi-rate ones never do
+  {
+    const int32_t ph[5] = {0, 1, 2, 3, 4};
+    const int N = 8, n_sub = 23;
+    for (SampledKind kind : {SampledKind::endpoints, SampledKind::tracking, SampledKind::endpoints_multirate,
+                             SampledKind::tracking_multirate})
+      for (int variant = 0; variant < 8; ++variant) {
+        const bool multi = multirate_kind(kind), track = tracking_kind(kind);
+        const bool noise = variant & 1, phase = track && (variant & 2), steps = variant & 4;
+        SampledCall c = good(kind);
+        c.G = 5;
+        c.num_steps = steps ? 10 : 0;
+        c.o.n_actual = steps ? 10 : 1;
+        c.goal.n_endpoints = track ? 0 : 3;
+        c.goal.L = track ? 50 : 0;
+        c.goal.ref_phase = phase ? ph : nullptr;
+        size_t by[SAMPLED_MULTIRATE_WS_COUNT], off[SAMPLED_MULTIRATE_WS_COUNT], want[SAMPLED_MULTIRATE_WS_COUNT],
+            want_off[SAMPLED_MULTIRATE_WS_COUNT];
+        sampled_call_ws_bytes(c, N, multi && steps ? n_sub : 0, noise, by);
+        const size_t total = carve(by, SAMPLED_MULTIRATE_WS_COUNT, off);
+        size_t want_total;
+        if (multi) {
+          sampled_multirate_ws_bytes(c.G, c.H, N, c.num_steps, steps ? n_sub : 0, c.goal.n_endpoints, c.o.n_actual, noise,
+                                     c.goal.L, c.goal.ref_stride, phase, want);
+          want_total = carve(want, SAMPLED_MULTIRATE_WS_COUNT, want_off);
+          for (int i = 0; i < SAMPLED_MULTIRATE_WS_COUNT; ++i) CHECK(by[i] == want[i] && off[i] == want_off[i]);
+        } else {
+          tracking_ws_bytes(c.G, c.H, N, c.num_steps, c.goal.n_endpoints, c.o.n_actual, noise, c.goal.L,
+                            c.goal.ref_stride, phase, want);
+          want_total = carve(want, TRACKING_WS_COUNT, want_off);
+          for (int i = 0; i < TRACKING_WS_COUNT; ++i) CHECK(by[i] == want[i] && off[i] == want_off[i]);
+          // max(n_sub, 1) lengths and history_rows of u and the path do not leak into this call
+          for (int i : {(int)SMWS_U, (int)SMWS_XPATH, (int)SMWS_SUBDT}) CHECK(by[i] == 0 && off[i] == total);
+        }
+        CHECK(total == want_total);
+        CHECK((by[SWS_NOISE] != 0) == (noise && steps));  // (no steps: no noise rows either)
+        CHECK((by[TWS_PHASE] != 0) == phase);
+        CHECK((by[TWS_REF] != 0) == track && (by[TWS_EE] != 0) == track);
+        for (int i : {(int)SWS_NOISE, (int)TWS_REF, (int)TWS_PHASE, (int)TWS_EE})
+          if (by[i] == 0) CHECK(off[i + 1] == off[i]);  // (none of them is the last sub-buffer)
+      }
   }
 
   if (bad) return 1;

@@ -8,7 +8,9 @@ N = 64, box rows), the notebook's 500-step closed loop (B = 1, N = 32), and the 
 3, N = 64, odd batches, adaptive rho, the closing tests after max_iter, each streaming kernel forced;
 and the sampled-wrench family at (G, H, N) = (2, 4, 8), 3 steps, direct and ADMM: mpc_run_sampled with
 noise, mpc_run_tracking with phases and noise, a controller session in both x0 forms with noise and
-its ctrl_end (every array of the returned dicts, keys fam_*).
+its ctrl_end, the multi-rate loops (shifted warm start, the residue sub-step, tracking), a group that
+stops with either plant, H = 256 (direct) and mpc_run_multirate (ADMM) (every array of the returned
+dicts, keys fam_*).
 cmp: per output, how many problems differ at all, the largest relative difference, for the
 closed loop the first step at which the goal distances differ, and per key of the family how many
 entries differ.
@@ -91,6 +93,7 @@ def dump(path):
 def family(_lib, m, ends):
     """The sampled-wrench entry points on fixed inputs: {fam_<mode>_<call>_<key>: array}."""
     from indy7_mpc_amd.utils import figure8
+    from oracle import rbd
     G, H, N, steps = 2, 4, 8, 3
     rng = np.random.default_rng(61)
     xs = np.concatenate([rng.uniform(-1, 1, (G, 6)), rng.uniform(-0.5, 0.5, (G, 6))], axis=1)
@@ -101,6 +104,18 @@ def family(_lib, m, ends):
     noise = rng.normal(0, 2.0, (steps, G * H, 3))
     ref = figure8(0.5, 0.55, [0, 0.4, 0.45], period=1.0, dt=0.01, cycles=3).reshape(-1, 6)
     kw = dict(keep_best=True, decay=0.97)
+    # (drawn after the inputs above, which stay what they were)
+    noise12 = rng.normal(0, 2.0, (12, G * H, 3))
+    fhyp256 = np.zeros((G, 256, 6))
+    fhyp256[:, :, :3] = rng.normal(0, 10.0, (G, 256, 3))
+    fhyp256[:, 0] = 0.0
+    fhyp256[np.arange(G), (np.arange(G) + 1) % H] = fact  # the actual wrench is among them
+    fhyp256 = fhyp256.reshape(G * 256, 6)
+    noise256 = rng.normal(0, 2.0, (2, G * 256, 3))
+    xs3 = np.concatenate([rng.uniform(-1, 1, (3, 6)), rng.uniform(-0.5, 0.5, (3, 6))], axis=1)
+    xs_stop = np.zeros((G, 12))
+    xs_stop[0, :6], xs_stop[1, :6] = 0.31, -0.4
+    ends_stop = np.array([rbd.eepos(np.full(6, 0.3)), rbd.eepos(np.full(6, 0.33))])
     out = {}
     for mode, qp in (("direct", _lib.QP_DIRECT), ("admm", _lib.QP_ADMM)):
         def handle():
@@ -123,6 +138,38 @@ def family(_lib, m, ends):
             r.update(h.ctrl_end())
             h.close()
             calls["ctrl_" + form] = r
+        # the multi-rate plant: two knots a step with the warm start shifted, the residue sub-step of
+        # sim_dt = 0.001 (step 9 is [0.001, 8.67e-19]), and tracking with 2.5 knots a step
+        h = handle()
+        calls["sampled_mr"] = h.mpc_run_sampled_multirate(xs, ends, steps, fhyp, fact, noise=noise, sim_dt=0.02,
+                                                          shift_warm_start=1, **kw)
+        h.close()
+        h = handle()
+        calls["sampled_mr_residue"] = h.mpc_run_sampled_multirate(xs, ends, 12, fhyp, fact, noise=noise12, sim_dt=0.001,
+                                                                  shift_warm_start=1, **kw)
+        h.close()
+        h = handle()
+        calls["tracking_mr"] = h.mpc_run_tracking_multirate(xs, ref, steps, fhyp, fact, ref_phase=[0, 17], noise=noise,
+                                                            sim_dt=0.025, **kw)
+        h.close()
+        # a group that stops mid-run (at rest within the radius of both endpoints: it switches, then
+        # stops), so the NaN / -1 layout is compared, with either plant
+        for call, run, sim_dt in (("sampled_stop", "mpc_run_sampled", 0.01), ("sampled_mr_stop", "mpc_run_sampled_multirate", 0.02)):
+            h = handle()
+            calls[call] = getattr(h, run)(xs_stop, ends_stop, 4, np.zeros((G * H, 6)), np.zeros((G, 6)), sim_dt=sim_dt)
+            h.close()
+        if mode == "direct":  # H = 256: the merge of four waves (H = 4 above: one partial wave)
+            h = _lib.Handle(m, N=N, max_batch=G * 256, qp_mode=qp)
+            calls["sampled_w4"] = h.mpc_run_sampled(xs, ends, 2, fhyp256, fact, noise=noise256, sim_dt=0.01, **kw)
+            h.close()
+            h = _lib.Handle(m, N=N, max_batch=G * 256, qp_mode=qp)
+            calls["sampled_mr_w4"] = h.mpc_run_sampled_multirate(xs, ends, 2, fhyp256, fact, noise=noise256, sim_dt=0.02,
+                                                                 shift_warm_start=1, **kw)
+            h.close()
+        else:  # the closed loops' shared reset: the multi-rate loop of whole instances
+            h = _lib.Handle(m, N=N, max_batch=3, qp_mode=qp)
+            calls["multirate"] = h.mpc_run_multirate(xs3, ends, 3, sim_dt=0.02)
+            h.close()
         for call, r in calls.items():
             for k, v in r.items():
                 out[f"fam_{mode}_{call}_{k}"] = np.asarray(v)
