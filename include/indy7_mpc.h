@@ -93,7 +93,9 @@ extern "C" {
 #define I7M_MAX_N 64
 
 /* ABI revision, returned by i7m_abi_version(); bumped whenever an existing signature, struct
- * layout, field meaning or enum count changes.  10: i7m_sampled_multirate_opts_default /
+ * layout, field meaning or enum count changes.  11: i7m_qp_policy, i7m_multirate_knots and the value
+ * I7M_CONTROL_POLICY of i7m_multirate_opts.control_from, which ABI 10 refused (appended; nothing
+ * existing changed).  10: i7m_sampled_multirate_opts_default /
  * i7m_mpc_run_sampled_multirate / i7m_mpc_run_tracking_multirate (appended; nothing existing
  * changed).  9: i7m_multirate_opts_default /
  * i7m_multirate_substeps / i7m_mpc_run_multirate (appended; nothing existing changed).  8: i7m_ctrl_begin / i7m_ctrl_step / i7m_ctrl_end
@@ -109,7 +111,7 @@ extern "C" {
  * 2: i7m_aba / i7m_rk4 take a wrench `frame` before their outputs and i7m_set_external_wrench a
  * trailing `frame` (0.2 builds); 1 had neither.  A caller built against another revision must not
  * call through this library: compare first. */
-#define I7M_ABI_VERSION 10
+#define I7M_ABI_VERSION 11
 
 #define I7M_OK 0
 #define I7M_EINVAL -1   /* bad argument (size, null pointer, unsupported N) */
@@ -264,6 +266,23 @@ int i7m_qp(i7m_handle* h, int32_t B, const double* xu, const double* xcur, const
 int i7m_qp_value(i7m_handle* h, int32_t B, const double* xu, const double* xcur, const double* goals,
                  int32_t goal_stride, double* V0);
 
+/* The QP's feedback policy (ABI 11): the time-varying LQR gains the exact solve's backward Riccati
+ * sweep computes, K~_k = -H^-1 G~ (6 x 13) of stages k = 0 .. n_k - 1, for the QP linearised at xu
+ * with xcur as the x_0 row, exactly as i7m_qp.  K_out (B, n_k, 6, 13) row-major: K_out[b, k, :, :12]
+ * is the gain K_k, K_out[b, k, :, 12] the feedforward, and the QP's minimiser satisfies u_k =
+ * K~_k [x_k; 1] in absolute coordinates (the QP variable is XU itself, l[:12] = -xs of
+ * src/osqp_solver.py:85), so that between solves u = u_k + K_k (x - x_k) is the QP's own answer to a
+ * state x off the planned x_k.  sol_out (B, T) or NULL: the minimiser, the buffer i7m_qp returns on
+ * an I7M_QP_DIRECT handle, bit for bit.  The reference has no counterpart: OSQP returns an iterate,
+ * not a policy.  I7M_QP_DIRECT and I7M_QP_ADMM: on an ADMM handle this is the exact QP's policy at
+ * that linearisation, which OSQP's iterate approximates, and the carried OSQP state is left
+ * untouched.  I7M_EINVAL with a message naming the argument, before any device work: an I7M_QP_BOX
+ * handle (its corrector steps overwrite the stored feedforward); n_k outside [1, N - 1]; null K_out,
+ * xu, xcur or goals; an open controller session.  Synchronous. */
+int i7m_qp_policy(i7m_handle* h, int32_t B, const double* xu, const double* xcur, const double* goals,
+                  int32_t goal_stride, int32_t n_k, double* K_out /* (B, n_k, 6, 13) */,
+                  double* sol_out /* (B, T) or NULL */);
+
 /* I7M_QP_BOX: interior-point record of the most recent QP of problems [0, B) (the last
  * i7m_qp, or the last SQP iteration of i7m_solve): corrector steps taken, 1 if converged
  * (mu < box_tol and residuals reduced by box_tol), final mu.  Any output may be NULL. */
@@ -336,6 +355,15 @@ int i7m_mpc_run(i7m_handle* h, int32_t B, const double* xstart, const double* en
 /* Options of i7m_mpc_run_multirate; fill with i7m_multirate_opts_default, then change fields. */
 #define I7M_CONTROL_NEW 0   /* the plant is driven by this step's solve: MPC_GATO_Batch, src/gato_mpc_batch.py:185 */
 #define I7M_CONTROL_PREV 1  /* by the warm start the solve started from: MPC_GATO, src/gato_mpc.py:126 */
+/* (ABI 11) by this step's solve under its own feedback policy; the reference has no counterpart.
+ * After the solve a policy pass linearises at xu_new with x_0 = xcur and runs the exact backward
+ * sweep (i7m_qp_policy's launches, in both QP modes); the sub-step that begins at plant state x with
+ * j knots of this step completed is driven by u = xu_new.u_j + K_j (x - xu_new.x_j), K_j the 6 x 12
+ * gain of stage j.  j advances where the schedule places a knot boundary (i7m_multirate_knots).  At
+ * x = xu_new.x_j the control is xu_new.u_j bit for bit, so a step's first sub-step runs under
+ * I7M_CONTROL_NEW's control.  Everything else of the step is as described below.  Refused in addition: a step
+ * that completes more than N - 2 knots (knot N - 1 has no control). */
+#define I7M_CONTROL_POLICY 2
 typedef struct i7m_multirate_opts {
   double sim_dt;        /* plant time per solve, finite and > 0, not bounded by dt; default 0.001
                            (src/gato_mpc_batch.py:76; MPC_GATO hard-codes 0.02, src/gato_mpc.py:76) */
@@ -349,6 +377,11 @@ int i7m_multirate_opts_default(i7m_multirate_opts* opts);
 /* Pure host: the total number of plant sub-steps of a run of num_steps MPC steps, to size
  * xpath_out; I7M_EINVAL with i7m_mpc_run_multirate's refusals of sim_dt. */
 int i7m_multirate_substeps(double dt, double sim_dt, int32_t N, int32_t num_steps, int32_t* n_sub);
+/* Pure host (ABI 11): knot_out[s] (n_sub entries, or NULL) = the knots its MPC step had completed when
+ * plant sub-step s began, 0 .. shift of the step: the knot whose control and gain drive the sub-step
+ * under I7M_CONTROL_POLICY.  I7M_EINVAL with i7m_mpc_run_multirate's refusals of sim_dt and
+ * control_from for that control_from, the N - 2 bound of I7M_CONTROL_POLICY among them. */
+int i7m_multirate_knots(double dt, double sim_dt, int32_t N, int32_t num_steps, int32_t control_from, int32_t* knot_out);
 
 /* Multi-rate closed loop of B independent instances on the device: MPC_GATO_Batch.run_mpc
  * (src/gato_mpc_batch.py:76-217) and, with other options, MPC_GATO.run_mpc (src/gato_mpc.py:53-150).
@@ -390,7 +423,7 @@ int i7m_multirate_substeps(double dt, double sim_dt, int32_t N, int32_t num_step
  * as its two staggered ranges, as i7m_mpc_run's.  I7M_QP_DIRECT and I7M_QP_ADMM; I7M_EINVAL with a
  * message naming the argument, before any device work: I7M_QP_BOX; an external wrench set on the
  * handle (neither driver's plant has one); sim_dt not finite or not positive; a step that completes
- * more than N - 1 knots; a step of more than 66 sub-steps (sim_dt > 64 dt); a bad control_from or
+ * more than N - 1 knots (N - 2 under I7M_CONTROL_POLICY); a step of more than 66 sub-steps (sim_dt > 64 dt); a bad control_from or
  * reset_what; null xstart, endpoints or dist_out. */
 int i7m_mpc_run_multirate(i7m_handle* h, int32_t B, const double* xstart, const double* endpoints, int32_t n_endpoints,
                           int32_t num_steps, const i7m_multirate_opts* opts, double* dist_out /* (steps,B) required */,
@@ -622,7 +655,7 @@ int i7m_mpc_run_tracking_multirate(i7m_handle* h, int32_t G, int32_t H, const do
  * session as it was.
  * While a session is open the entry points that would overwrite its rows, goals, wrenches or
  * solver state are refused ("controller session open"): i7m_solve, i7m_solve_device, i7m_qp,
- * i7m_qp_value, i7m_linearize, i7m_merit, i7m_linesearch, the six i7m_mpc_run*,
+ * i7m_qp_value, i7m_qp_policy, i7m_linearize, i7m_merit, i7m_linesearch, the six i7m_mpc_run*,
  * i7m_set_external_wrench, i7m_reset, i7m_admm_reset, i7m_set_stream.  The getters, the timing
  * calls, i7m_synchronize and the query hooks (i7m_eepos, i7m_aba, i7m_aba_derivatives, i7m_rk4:
  * they use scratch the session does not rely on between steps) stay available. */

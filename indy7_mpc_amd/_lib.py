@@ -20,7 +20,7 @@ import numpy as np
 LIB_DIR = os.path.join(os.path.dirname(os.path.abspath(__file__)), "lib")
 LIB_PATH = os.environ.get("I7M_LIB", os.path.join(LIB_DIR, "libindy7mpc.so"))  # I7M_LIB: A/B builds
 
-ABI_VERSION = 10  # I7M_ABI_VERSION of include/indy7_mpc.h this binding's SIGNATURES follow
+ABI_VERSION = 11  # I7M_ABI_VERSION of include/indy7_mpc.h this binding's SIGNATURES follow
 NJ, NX, NU = 6, 12, 6
 MAX_SQP = 8
 MAX_N = 64
@@ -96,8 +96,9 @@ ADMM_DEFAULTS = dict(rho=0.1, sigma=1e-6, alpha=1.6, eps_abs=1e-3, eps_rel=1e-3,
                      scaling=10, check_dualgap=True, adaptive_rho_interval=0, adaptive_rho_tolerance=5.0)
 PIPE_AUTO, PIPE_SPLIT, PIPE_FUSED, PIPE_FUSED_ITER = 0, 1, 2, 3
 WRENCH_LOCAL, WRENCH_WORLD = 0, 1
-CONTROL_NEW, CONTROL_PREV = 0, 1  # i7m_multirate_opts.control_from
-_CONTROLS = {"new": CONTROL_NEW, "prev": CONTROL_PREV, CONTROL_NEW: CONTROL_NEW, CONTROL_PREV: CONTROL_PREV}
+CONTROL_NEW, CONTROL_PREV, CONTROL_POLICY = 0, 1, 2  # i7m_multirate_opts.control_from
+_CONTROLS = {"new": CONTROL_NEW, "prev": CONTROL_PREV, "policy": CONTROL_POLICY, CONTROL_NEW: CONTROL_NEW,
+             CONTROL_PREV: CONTROL_PREV, CONTROL_POLICY: CONTROL_POLICY}
 MULTIRATE_MAX_SUB = 66  # i7m_plan.h
 _FRAMES = {"local": WRENCH_LOCAL, "world": WRENCH_WORLD, WRENCH_LOCAL: WRENCH_LOCAL, WRENCH_WORLD: WRENCH_WORLD}
 BOX_Q, BOX_V, BOX_U = 1, 2, 4
@@ -168,6 +169,7 @@ SIGNATURES = [
                                    C.c_void_p]),
     ("i7m_qp", C.c_int, [_H, C.c_int32, _DP, _DP, _DP, C.c_int32, _DP]),
     ("i7m_qp_value", C.c_int, [_H, C.c_int32, _DP, _DP, _DP, C.c_int32, _DP]),
+    ("i7m_qp_policy", C.c_int, [_H, C.c_int32, _DP, _DP, _DP, C.c_int32, C.c_int32, _DP, _DP]),
     ("i7m_get_box_stats", C.c_int, [_H, C.c_int32, C.POINTER(C.c_int32), C.POINTER(C.c_int32), _DP]),
     ("i7m_admm_reset", C.c_int, [_H, C.c_int32, C.c_int32]),
     ("i7m_get_admm_stats", C.c_int, [_H, C.c_int32, C.POINTER(C.c_int32), _DP]),
@@ -184,6 +186,7 @@ SIGNATURES = [
     ("i7m_mpc_run", C.c_int, [_H, C.c_int32, _DP, _DP, C.c_int32, C.c_int32, _DP, _DP, _DP, _DP]),
     ("i7m_multirate_opts_default", C.c_int, [C.POINTER(i7m_multirate_opts)]),
     ("i7m_multirate_substeps", C.c_int, [C.c_double, C.c_double, C.c_int32, C.c_int32, _IP32]),
+    ("i7m_multirate_knots", C.c_int, [C.c_double, C.c_double, C.c_int32, C.c_int32, C.c_int32, _IP32]),
     ("i7m_mpc_run_multirate", C.c_int, [_H, C.c_int32, _DP, _DP, C.c_int32, C.c_int32, C.POINTER(i7m_multirate_opts),
                                         _DP, _DP, _DP, _DP, _DP, _DP]),
     ("i7m_sampled_opts_default", C.c_int, [C.POINTER(i7m_sampled_opts)]),
@@ -272,18 +275,20 @@ def _iptr(a):
     return None if a is None else a.ctypes.data_as(_IP32)
 
 
-def multirate_schedule(dt, sim_dt, num_steps, N=None):
+def multirate_schedule(dt, sim_dt, num_steps, N=None, knots=False):
     """The plant's sub-steps of a multi-rate run (i7m_plan.h multirate_schedule, the same double
     arithmetic in the same order: the reference's inner while-loop, src/gato_mpc_batch.py:171-199):
     (sub_start (num_steps + 1,) int32, sub_dt (S,), shift (num_steps,) int32).  Step i owns sub-steps
     [sub_start[i], sub_start[i + 1]) and completes shift[i] knots.  The float residues are kept
     (dt 0.01, sim_dt 0.001: step 9 is [0.001, 8.67e-19]).  ValueError for what the library refuses:
     sim_dt not finite or not positive, more than MULTIRATE_MAX_SUB sub-steps in a step and, with N
-    given, a step that completes more than N - 1 knots."""
+    given, a step that completes more than N - 1 knots.  knots=True appends sub_knot (S,) int32
+    (i7m_multirate_knots): the knots its step had completed when the sub-step began, the knot whose
+    control and gain drive it under control_from="policy"."""
     dt, sim_dt = float(dt), float(sim_dt)
     if not np.isfinite(sim_dt) or not sim_dt > 0.0:
         raise ValueError("sim_dt must be finite and > 0")
-    sub_start, sub_dt, shift = [0], [], []
+    sub_start, sub_dt, shift, sub_knot = [0], [], [], []
     acc = 0.0  # carried over all steps
     for i in range(int(num_steps)):
         rem, sh, n = sim_dt, 0, 0
@@ -295,6 +300,7 @@ def multirate_schedule(dt, sim_dt, num_steps, N=None):
             acc += ts
             rem -= ts
             sub_dt.append(ts)
+            sub_knot.append(sh)
             if abs(acc - dt) < 1e-10:
                 sh += 1
                 acc = 0.0
@@ -302,7 +308,19 @@ def multirate_schedule(dt, sim_dt, num_steps, N=None):
             raise ValueError(f"sim_dt = {sim_dt} completes more than N - 1 = {N - 1} knots in step {i}")
         shift.append(sh)
         sub_start.append(len(sub_dt))
-    return np.array(sub_start, dtype=np.int32), np.array(sub_dt, dtype=np.float64), np.array(shift, dtype=np.int32)
+    out = (np.array(sub_start, dtype=np.int32), np.array(sub_dt, dtype=np.float64), np.array(shift, dtype=np.int32))
+    return out + (np.array(sub_knot, dtype=np.int32),) if knots else out
+
+
+def multirate_knots(dt, sim_dt, N, num_steps, control_from="policy"):
+    """i7m_multirate_knots (pure host): the library's knot index per plant sub-step, (S,) int32; raises
+    I7MError for what i7m_mpc_run_multirate refuses of sim_dt under that control_from."""
+    lib = load()
+    n_sub = C.c_int32(0)
+    _check(lib.i7m_multirate_substeps(float(dt), float(sim_dt), int(N), int(num_steps), C.byref(n_sub)))
+    kn = np.zeros(n_sub.value, dtype=np.int32)
+    _check(lib.i7m_multirate_knots(float(dt), float(sim_dt), int(N), int(num_steps), _CONTROLS[control_from], _iptr(kn)))
+    return kn
 
 
 class Handle:
@@ -409,6 +427,18 @@ class Handle:
         V = np.empty((B, 13, 13))
         _check(self._lib.i7m_qp_value(self._h, B, _ptr(xu), _ptr(xc), _ptr(goals), stride, _ptr(V)))
         return V
+
+    def qp_policy(self, xu, xcur, goals, n_k, want_sol=False):
+        """The QP's feedback policy (i7m_qp_policy): K (B, n_k, 6, 13), K[b, k, :, :12] the gain K_k and
+        K[b, k, :, 12] the feedforward of the exact QP linearised at xu with x_0 = xcur, whose
+        minimiser satisfies u_k = K~_k [x_k; 1].  want_sol: also the minimiser (B, T), i7m_qp's buffer.
+        I7M_QP_DIRECT and I7M_QP_ADMM handles (the carried OSQP state is left untouched)."""
+        xu, goals, B, stride, xc = self._batch(xu, goals, xcur)
+        n_k = int(n_k)
+        K = np.empty((B, max(n_k, 0), NU, NX + 1))
+        sol = np.empty_like(xu) if want_sol else None
+        _check(self._lib.i7m_qp_policy(self._h, B, _ptr(xu), _ptr(xc), _ptr(goals), stride, n_k, _ptr(K), _ptr(sol)))
+        return (K, sol) if want_sol else K
 
     def box_stats(self, B):
         """Interior-point record of the last QP (box mode): (iters, converged, mu), each (B,)."""
@@ -531,8 +561,9 @@ class Handle:
                           reset_what=ADMM_RESET_ALL):
         """Multi-rate closed loop of B instances on the device (i7m_mpc_run_multirate): the plant
         advances sim_dt per solve against the knot grid dt, split at knot boundaries, the warm start
-        shifted by the knots each step completes.  control_from "new" (MPC_GATO_Batch) or "prev"
-        (MPC_GATO).  Returns a dict: dist (num_steps, B), q and u (num_steps, B, 6), xpath (S, B, 6)
+        shifted by the knots each step completes.  control_from "new" (MPC_GATO_Batch), "prev"
+        (MPC_GATO) or "policy" (the solve's controls under its own Riccati feedback gains, u = u_j +
+        K_j (x - x_j) per plant sub-step; no counterpart in the reference).  Returns a dict: dist (num_steps, B), q and u (num_steps, B, 6), xpath (S, B, 6)
         one q per plant sub-step, xcur (B, 12), xu (B, T), and the schedule the library ran, from
         i7m_multirate_substeps and the same arithmetic here: sub_start (num_steps + 1,), shift
         (num_steps,) (step i wrote xpath[sub_start[i]:sub_start[i + 1]]).  NaN from an instance's stop on."""

@@ -28,6 +28,7 @@
 #include "i7m_ctrl.h"
 #include "i7m_mpc_multirate.h"
 #include "i7m_mpc_sampled_multirate.h"
+#include "i7m_mpc_policy.h"
 #include "i7m_plan.h"
 
 // Source hash of the tree this library was built from (__graft_entry__.build passes it), so
@@ -64,9 +65,15 @@ hipError_t i7m_prepare_sqp_fused(int dev, int N);
 hipError_t i7m_launch_multirate_step(int n, hipStream_t s, const void* model, const void* args);
 // i7m_mpc_sampled_multirate_tu.hip (k_sampled_multirate_step); args: const SampledMultirateArgs*
 hipError_t i7m_launch_sampled_multirate_step(int ng, int H, hipStream_t s, const void* model, const void* args);
+// i7m_mpc_policy_tu.hip (k_policy_gather, k_mpc_multirate_policy_step); args: const MultirateArgs*,
+// knots: const PolicyKnots*
+hipError_t i7m_launch_policy_gather(int B, int N, int n_k, hipStream_t s, const double* kbuf, double* K_out);
+hipError_t i7m_launch_multirate_policy_step(int n, hipStream_t s, const void* model, const void* args, const void* knots,
+                                            const double* kbuf);
 
 static_assert(sizeof(i7m_problem_stats) == sizeof(ProblemStats), "stats layout");
 static_assert(ADMM_RES_MAX_N == ARES_N, "i7m_plan.h: k_admm_iter_res's horizon");
+static_assert(POLICY_MAX_SUB == MULTIRATE_MAX_SUB, "i7m_mpc_policy.h: PolicyKnots holds one step's sub-steps");
 
 namespace {
 
@@ -150,6 +157,9 @@ struct i7m_handle {
   int ablate = 0;                  // I7M_DIAG builds only (I7M_ABLATE): timing variants, results invalid
   bool spec = false;               // model == kIndy7Model: use the kernels with the constants baked in
   bool has_fext = false;
+  // I7M_POLICY_ZERO_K=1 at i7m_create (a test switch): I7M_CONTROL_POLICY steps with the policy
+  // pass's gains zeroed, so the run must equal I7M_CONTROL_NEW's bit for bit
+  bool policy_zero_k = false;
   size_t goal_cap = 0;
   // hipGraph replay of run_sqp (run_sqp_graphed): a few instantiated graphs keyed by the call
   struct GraphEntry {
@@ -623,6 +633,17 @@ int solve_qp(i7m_handle* h, hipStream_t s, const Bufs& W, const SolveParams& P, 
   }
   *out = W.bx;
   return I7M_OK;
+}
+
+// The policy pass (i7m_qp_policy, I7M_CONTROL_POLICY): linearise at xu with x_0 = xs, then the exact
+// backward sweep and rollout, in every QP mode the launches of an I7M_QP_DIRECT QP.  Leaves the gains
+// K~_k of the range's problems in W.kbuf and the QP's minimiser in W.sol; on an I7M_QP_ADMM handle
+// the carried OSQP state (h->d_admm) is neither read nor written.
+int policy_pass(i7m_handle* h, hipStream_t s, const Bufs& W, const SolveParams& P, const double* xu, const double* xs,
+                const double* goals) {
+  const int rc = launch_linearize(h, s, W, P, xu, goals, nullptr);
+  if (rc) return rc;
+  return launch_riccati(h, s, W, P, xu, xs, nullptr, W.sol);
 }
 
 int launch_fused(i7m_handle* h, hipStream_t s, const Bufs& W, const SolveParams& P, const double* xu_in, double* xu_out,
@@ -1262,6 +1283,7 @@ int i7m_create(const i7m_config* cfg, i7m_handle** out) {
     return bail(fail(I7M_EINVAL, "I7M_ABLATE is set, but this is the release library: the ablation "
                                  "timing kernels exist only in the -DI7M_DIAG build (tools/)"));
 #endif
+  if (const char* e = std::getenv("I7M_POLICY_ZERO_K")) h->policy_zero_k = std::atoi(e) != 0;
   std::string tune_err;
   if (!tuning_from_env(*cfg, &h->tune, &tune_err)) return bail(fail(I7M_EINVAL, tune_err));
   if (hipStreamCreateWithFlags(&h->cs[0], hipStreamNonBlocking) != hipSuccess ||
@@ -1516,6 +1538,35 @@ int i7m_qp_value(i7m_handle* h, int32_t B, const double* xu, const double* xcur,
   return i7m_synchronize(h);
 }
 
+int i7m_qp_policy(i7m_handle* h, int32_t B, const double* xu, const double* xcur, const double* goals, int32_t goal_stride,
+                  int32_t n_k, double* K_out, double* sol_out) {
+  const std::string who = "i7m_qp_policy";
+  int rc = check_batch(h, B, goal_stride);
+  if (rc) return rc;
+  // the box mode's corrector steps overwrite kbuf's feedforward column (riccati_mfma_body, kff_only)
+  if (h->cfg.qp_mode == I7M_QP_BOX) return fail(I7M_EINVAL, who + ": I7M_QP_BOX is not supported (I7M_QP_DIRECT or I7M_QP_ADMM)");
+  const int N = (int)h->N;
+  if (n_k < 1 || n_k > N - 1)
+    return fail(I7M_EINVAL, who + ": n_k = " + std::to_string(n_k) + " outside [1, N - 1 = " + std::to_string(N - 1) + "]");
+  if (!K_out) return fail(I7M_EINVAL, who + ": null K_out");
+  if (B == 0) return I7M_OK;
+  if (!xu) return fail(I7M_EINVAL, who + ": null xu");
+  if (!xcur) return fail(I7M_EINVAL, who + ": null xcur");
+  if (!goals) return fail(I7M_EINVAL, who + ": null goals");
+  HIPCHK(hipSetDevice(h->dev));
+  const SolveParams P = params_of(h, B, goal_stride);
+  const Bufs W = bufs_at(h, 0);
+  if ((rc = stage_in(h, 0, B, xu, xcur, goals, goal_stride))) return rc;
+  if ((rc = policy_pass(h, h->stream, W, P, h->d_xu, h->d_xs, h->d_goal))) return rc;
+  // gathered into the linearisation's rows, dead once the sweep and rollout have run:
+  // B n_k 78 <= max_batch (N - 1) LIN_STRIDE doubles
+  double* kout = W.lin;
+  HIPCHK(i7m_launch_policy_gather(B, N, n_k, h->stream, W.kbuf, kout));
+  if ((rc = copy_out(h, K_out, kout, (size_t)B * n_k * POLICY_K))) return rc;
+  if (sol_out && (rc = copy_out(h, sol_out, W.sol, (size_t)B * h->T))) return rc;
+  return i7m_synchronize(h);
+}
+
 int i7m_get_box_stats(i7m_handle* h, int32_t B, int32_t* iters, int32_t* converged, double* mu) {
   if (!h) return fail(I7M_EINVAL, "null handle");
   if (h->cfg.qp_mode != I7M_QP_BOX) return fail(I7M_EINVAL, "handle is not in I7M_QP_BOX mode");
@@ -1700,6 +1751,22 @@ int i7m_multirate_substeps(double dt, double sim_dt, int32_t N, int32_t num_step
   return I7M_OK;
 }
 
+int i7m_multirate_knots(double dt, double sim_dt, int32_t N, int32_t num_steps, int32_t control_from, int32_t* knot_out) {
+  const std::string who = "multirate_knots";
+  if (num_steps < 0) return fail(I7M_EINVAL, who + ": num_steps = " + std::to_string(num_steps) + ", need num_steps >= 0");
+  if (control_from != I7M_CONTROL_NEW && control_from != I7M_CONTROL_PREV && control_from != I7M_CONTROL_POLICY)
+    return fail(I7M_EINVAL, who + ": control_from must be I7M_CONTROL_NEW, I7M_CONTROL_PREV or I7M_CONTROL_POLICY");
+  MultirateSchedule sch;
+  const char* which = "";
+  long at = 0;
+  if (!multirate_schedule(dt, sim_dt, N, num_steps, &sch, &which, &at))
+    return fail(I7M_EINVAL, multirate_refusal(who, which, at, sim_dt, N));
+  if (control_from == I7M_CONTROL_POLICY && (at = multirate_policy_bad_step(sch, N)) >= 0)
+    return fail(I7M_EINVAL, multirate_policy_refusal(who, at, sim_dt, N));
+  if (knot_out) std::copy(sch.sub_knot.begin(), sch.sub_knot.end(), knot_out);
+  return I7M_OK;
+}
+
 int i7m_mpc_run_multirate(i7m_handle* h, int32_t B, const double* xstart, const double* endpoints, int32_t n_endpoints,
                           int32_t num_steps, const i7m_multirate_opts* opts, double* dist_out, double* q_out,
                           double* u_out, double* xpath_out, double* xcur_out, double* xu_out) {
@@ -1713,8 +1780,8 @@ int i7m_mpc_run_multirate(i7m_handle* h, int32_t B, const double* xstart, const 
     return fail(I7M_EINVAL, who + ": I7M_QP_BOX is not supported (I7M_QP_DIRECT or I7M_QP_ADMM)");
   if (n_endpoints < 1) return fail(I7M_EINVAL, who + ": n_endpoints = " + std::to_string(n_endpoints) + ", need >= 1 endpoint");
   if (num_steps < 0) return fail(I7M_EINVAL, who + ": num_steps = " + std::to_string(num_steps) + ", need num_steps >= 0");
-  if (o.control_from != I7M_CONTROL_NEW && o.control_from != I7M_CONTROL_PREV)
-    return fail(I7M_EINVAL, who + ": control_from must be I7M_CONTROL_NEW or I7M_CONTROL_PREV");
+  if (o.control_from != I7M_CONTROL_NEW && o.control_from != I7M_CONTROL_PREV && o.control_from != I7M_CONTROL_POLICY)
+    return fail(I7M_EINVAL, who + ": control_from must be I7M_CONTROL_NEW, I7M_CONTROL_PREV or I7M_CONTROL_POLICY");
   if (o.reset_what & ~I7M_ADMM_RESET_ALL) return fail(I7M_EINVAL, who + ": reset_what has unknown I7M_ADMM_RESET_* bits");
   if (!std::isfinite(o.goal_radius)) return fail(I7M_EINVAL, who + ": goal_radius must be finite");
   if (!xstart) return fail(I7M_EINVAL, who + ": null xstart");
@@ -1731,6 +1798,9 @@ int i7m_mpc_run_multirate(i7m_handle* h, int32_t B, const double* xstart, const 
   long at = 0;
   if (!multirate_schedule(h->cfg.dt, o.sim_dt, N, num_steps, &sch, &which, &at))
     return fail(I7M_EINVAL, multirate_refusal(who, which, at, o.sim_dt, N));
+  const bool policy = o.control_from == I7M_CONTROL_POLICY;
+  if (policy && (at = multirate_policy_bad_step(sch, N)) >= 0)
+    return fail(I7M_EINVAL, multirate_policy_refusal(who, at, o.sim_dt, N));
   if (B == 0) return I7M_OK;
   HIPCHK(hipSetDevice(h->dev));
   const size_t T = h->T;
@@ -1782,6 +1852,17 @@ int i7m_mpc_run_multirate(i7m_handle* h, int32_t B, const double* xstart, const 
       a.q_out = d_q + ((size_t)i * B + lo) * 6;
       a.u_out = d_u + ((size_t)i * B + lo) * 6;
       a.xpath_out = d_xp + ((size_t)sch.sub_start[i] * B + lo) * 6;
+      if (policy) {
+        // the gains of this step's solve: the QP at xu_new with x_0 = xcur, on this range's rows and
+        // stream behind its solve (in I7M_QP_ADMM the exact QP's, which OSQP's iterate approximates)
+        const Bufs W = bufs_at(h, lo);
+        if ((rc3 = policy_pass(h, s, W, params_of(h, n, 3), out, xs, g))) return rc3;
+        if (h->policy_zero_k) HIPCHK(hipMemsetAsync(W.kbuf, 0, (size_t)n * (N - 1) * KBUF_STRIDE * 8, s));
+        PolicyKnots kn{};
+        for (int e = 0; e < a.n_sub; ++e) kn.j[e] = (unsigned char)sch.sub_knot[sch.sub_start[i] + e];
+        HIPCHK(i7m_launch_multirate_policy_step(n, s, h->d_model, &a, &kn, W.kbuf));
+        continue;
+      }
       HIPCHK(i7m_launch_multirate_step(n, s, h->d_model, &a));
     }
     return I7M_OK;

@@ -303,12 +303,13 @@ inline void sampled_ws_bytes(int G, int H, int N, int num_steps, int n_endpoints
 // real rk4 call and a real xpath entry there too.
 // The reference's current_interval = int(time_accumulated / dt) (:179 / :125) is always 0: the
 // accumulator is reset whenever it reaches dt, so it stays below dt.  Every sub-step is driven by
-// knot 0's control and no knot index is carried.
+// knot 0's control and no knot index is carried (sub_knot below is I7M_CONTROL_POLICY's alone).
 constexpr int MULTIRATE_MAX_SUB = 66;  // sub-steps of one MPC step: covers sim_dt <= 64 dt (64 whole knots, two partial)
 struct MultirateSchedule {
   std::vector<int32_t> sub_start;  // (num_steps + 1) step i owns sub-steps [sub_start[i], sub_start[i + 1])
   std::vector<double> sub_dt;      // (S) rk4 step lengths
   std::vector<int32_t> shift;      // (num_steps) knots completed in step i: the warm-start shift
+  std::vector<int32_t> sub_knot;   // (S) knots its step had completed when the sub-step began (I7M_CONTROL_POLICY)
   int total() const { return sub_start.empty() ? 0 : sub_start.back(); }
 };
 // False with *which = "sim_dt" (not finite or not positive), "shift" (step *at completes more than
@@ -335,6 +336,7 @@ inline bool multirate_schedule(double dt, double sim_dt, int N, int num_steps, M
       acc += ts;
       rem -= ts;
       out->sub_dt.push_back(ts);
+      out->sub_knot.push_back(shift);
       if (std::fabs(acc - dt) < 1e-10) {
         ++shift;
         acc = 0.0;
@@ -356,6 +358,17 @@ inline std::string multirate_refusal(const std::string& who, const std::string& 
     return who + ": sim_dt = " + sd + " needs more than MULTIRATE_MAX_SUB = " + std::to_string(MULTIRATE_MAX_SUB) +
            " plant sub-steps in step " + step;
   return who + ": sim_dt must be finite and > 0";
+}
+// I7M_CONTROL_POLICY drives sub-step s with knot sub_knot[s]'s control and gain, and knot N - 1 has
+// neither: the first step that completes more than N - 2 knots, or -1.
+inline long multirate_policy_bad_step(const MultirateSchedule& sch, int N) {
+  for (size_t i = 0; i < sch.shift.size(); ++i)
+    if (sch.shift[i] > N - 2) return (long)i;
+  return -1;
+}
+inline std::string multirate_policy_refusal(const std::string& who, long at, double sim_dt, int N) {
+  return who + ": sim_dt = " + std::to_string(sim_dt) + " completes more than N - 2 = " + std::to_string(N - 2) +
+         " knots in step " + std::to_string(at) + " (control_from = I7M_CONTROL_POLICY: knot N - 1 has no control)";
 }
 // i7m_mpc_run_multirate's request: the endpoints; the distance, q and control histories (per step)
 // and the path (per sub-step); the sub-step lengths; the instances' initial rho (I7M_QP_ADMM

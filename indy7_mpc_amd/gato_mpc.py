@@ -26,8 +26,8 @@ class MPC_GATO(MPC_GATO_Batch):
     GOAL_RADIUS = 1e-2
     CONTROL_FROM = "prev"
 
-    def __init__(self, model=None, N=32, dt=0.01, qp_mode="admm", device_id=0):
-        super().__init__(model, N, dt, 1, qp_mode, device_id)
+    def __init__(self, model=None, N=32, dt=0.01, qp_mode="admm", device_id=0, feedback=False):
+        super().__init__(model, N, dt, 1, qp_mode, device_id, feedback)
 
     @property
     def solver(self):

@@ -83,7 +83,11 @@ class MPC_GATO_Batch:
     GOAL_RADIUS = 0.1
     CONTROL_FROM = "new"
 
-    def __init__(self, model=None, N=32, dt=0.01, batch_size=4, qp_mode="admm", device_id=0):
+    def __init__(self, model=None, N=32, dt=0.01, batch_size=4, qp_mode="admm", device_id=0, feedback=False):
+        """feedback=True: the plant runs under the solve's own Riccati feedback policy, u = u_j + K_j
+        (x - x_j) per plant sub-step (``I7M_CONTROL_POLICY``), where the reference holds knot 0's
+        control until the next solve; the default is the reference's behaviour."""
+        self.feedback = bool(feedback)
         self.qp_mode = _sampling.qp_mode_of(batch_size, qp_mode)
         self.model = model or default_model()
         self.N, self.dt, self.batch_size = int(N), float(dt), int(batch_size)
@@ -123,7 +127,8 @@ class MPC_GATO_Batch:
         h = self._handle(B)
         t0 = time.perf_counter()
         r = h.mpc_run_multirate(xs, endpoints, num_steps, sim_dt=sim_dt, goal_radius=self.GOAL_RADIUS,
-                                control_from=self.CONTROL_FROM, reset_what=_lib.ADMM_RESET_ALL)
+                                control_from="policy" if self.feedback else self.CONTROL_FROM,
+                                reset_what=_lib.ADMM_RESET_ALL)
         per_step = (time.perf_counter() - t0) / max(num_steps, 1)
         ran = np.isfinite(r["xpath"][:, :, 0])  # an instance's path ends with the step before its stop
         xpaths = [[q for q in r["xpath"][ran[:, b], b]] for b in range(B)]
