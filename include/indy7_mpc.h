@@ -93,7 +93,10 @@ extern "C" {
 #define I7M_MAX_N 64
 
 /* ABI revision, returned by i7m_abi_version(); bumped whenever an existing signature, struct
- * layout, field meaning or enum count changes.  11: i7m_qp_policy, i7m_multirate_knots and the value
+ * layout, field meaning or enum count changes.  12: i7m_sampled_multirate_opts' former `pad` is
+ * `control_from` (same layout; 0 is what every earlier caller wrote there and means what it did),
+ * i7m_ctrl_set_policy / i7m_ctrl_get_policy / i7m_ctrl_set_applied (appended; nothing existing
+ * changed).  11: i7m_qp_policy, i7m_multirate_knots and the value
  * I7M_CONTROL_POLICY of i7m_multirate_opts.control_from, which ABI 10 refused (appended; nothing
  * existing changed).  10: i7m_sampled_multirate_opts_default /
  * i7m_mpc_run_sampled_multirate / i7m_mpc_run_tracking_multirate (appended; nothing existing
@@ -111,7 +114,7 @@ extern "C" {
  * 2: i7m_aba / i7m_rk4 take a wrench `frame` before their outputs and i7m_set_external_wrench a
  * trailing `frame` (0.2 builds); 1 had neither.  A caller built against another revision must not
  * call through this library: compare first. */
-#define I7M_ABI_VERSION 11
+#define I7M_ABI_VERSION 12
 
 #define I7M_OK 0
 #define I7M_EINVAL -1   /* bad argument (size, null pointer, unsupported N) */
@@ -532,7 +535,10 @@ typedef struct i7m_sampled_multirate_opts {
   int32_t shift_warm_start; /* 1: the rows' warm start is shifted by the knots a step completes
                            (src/gato_mpc_batch.py:202-203's rule); default 0, as the reference's shift
                            is commented out (src/gato_mpc_batch_sample.py:194-201) */
-  int32_t pad;          /* 0 */
+  int32_t control_from; /* (ABI 12, was `pad`: same layout) I7M_CONTROL_NEW (0, default): the plant holds
+                           XU_best's first control over the step; I7M_CONTROL_POLICY (2): the plant runs
+                           under the winner's feedback policy, see below.  Anything else, I7M_CONTROL_PREV
+                           included (these loops have no such variant), is refused */
 } i7m_sampled_multirate_opts;
 int i7m_sampled_multirate_opts_default(i7m_sampled_multirate_opts* opts);
 
@@ -573,6 +579,23 @@ int i7m_sampled_multirate_opts_default(i7m_sampled_multirate_opts* opts);
  *              then the same rk4 code), and a hypothesis equal to the actual wrench scores as in
  *              i7m_mpc_run_sampled.  The lowest index wins a tie, a NaN error never wins; then the
  *              resample.
+ * opts->control_from = I7M_CONTROL_POLICY (ABI 12; the reference has no counterpart): behind every
+ * solve, the initial one included, the policy pass of i7m_qp_policy runs on every row (the QP at
+ * that solve's result with x_0 = the row's state and the row's own wrench: the resample comes
+ * later, in the select), and plant and score of a step change:
+ *     plant    sub-step s begins at plant state x with j = the knots this step has completed
+ *              (i7m_multirate_knots) and is driven by u_s = XU_best[g].u_j + K_j (x - XU_best[g].x_j),
+ *              K_j the gain of stage j of row g H + best (row 0 after the initial solve), K_j dx in
+ *              the fixed order of i7m_mpc_run_multirate's policy plant.  u_out[i, g] stays
+ *              XU_best[g][12:18], the nominal first control.
+ *     select   the torque varies within the step, so hypothesis h is scored by REPLAYING the step:
+ *              from x_last the same sub-steps of the same lengths under the recorded controls u_s
+ *              (the plant's, not recomputed from the replayed state), wrench row h converted once at
+ *              x_last's q; err_h = |replay - xcur[g]|_2.  Plant and replay are the same code: a
+ *              hypothesis equal to the actual wrench scores exactly 0 on every step.
+ * Refused in addition: a step that completes more than N - 2 knots (knot N - 1 has no control), with
+ * i7m_mpc_run_multirate's text.  I7M_POLICY_ZERO_K=1 at i7m_create zeroes the gains here too.  The
+ * single-rate entry points i7m_mpc_run_sampled / i7m_mpc_run_tracking have no such option.
  * Deliberately not reproduced: the actual force's random walk (:244-250; the caller supplies
  * f_actual); the notebook's use of the world force as a local one (its actInv is commented out);
  * np.random's global draw order.
@@ -583,7 +606,8 @@ int i7m_sampled_multirate_opts_default(i7m_sampled_multirate_opts* opts);
  * solve.  Synchronous.  I7M_EINVAL with the argument named, before any device work: everything
  * i7m_mpc_run_sampled / i7m_mpc_run_tracking refuse except sim_dt > dt; sim_dt not finite or not
  * positive; a step of more than 66 sub-steps; a step that completes more than N - 1 knots;
- * shift_warm_start not 0 or 1; an open controller session; I7M_QP_BOX. */
+ * shift_warm_start not 0 or 1; control_from other than I7M_CONTROL_NEW or I7M_CONTROL_POLICY; an
+ * open controller session; I7M_QP_BOX. */
 int i7m_mpc_run_sampled_multirate(i7m_handle* h, int32_t G, int32_t H, const double* xstart, const double* endpoints,
                                   int32_t n_endpoints, int32_t num_steps, const double* fhyp, const double* f_actual,
                                   const double* noise, const i7m_sampled_multirate_opts* opts,
@@ -640,7 +664,33 @@ int i7m_mpc_run_tracking_multirate(i7m_handle* h, int32_t G, int32_t H, const do
  * (G) int32, fbest_out (G, 6), err_out (G), ee_out (G, 3) may be NULL.  A step allocates nothing:
  * everything it needs, pinned host staging included, is allocated by i7m_ctrl_begin.  It runs as
  * ONE range on the handle's stream (a session gets no two-stream stagger, whatever G H is), ends
- * with one device-to-host copy and one synchronisation, and captures no graph.
+ * with one device-to-host copy (two with the policy on, below) and one synchronisation, and
+ * captures no graph.
+ *
+ * The winner's feedback policy (ABI 12).  A torque loop that runs faster than the solver has one
+ * torque vector per step to apply; the session can hand out the time-varying gains of the winning
+ * row so that it applies u_k + K_k (x - x_k) between solves instead.
+ *   i7m_ctrl_set_policy(h, n_k)   n_k in [0, N - 1]; 0 is off, the state after i7m_ctrl_begin.
+ *            Allocates a device buffer (G, n_k, 96) and pinned staging of that size, recorded on the
+ *            session and freed by i7m_ctrl_end / i7m_destroy (a step still allocates nothing).  With
+ *            the policy on, a step runs the policy pass of i7m_qp_policy over all G H rows behind
+ *            its solve and before the select (the rows' wrenches are still the solve's), and after
+ *            the select one small launch copies, for k < n_k, K~_k of row g H + best and
+ *            XU_best[g][18 k : 18 k + 18] into that buffer; the step then ends with two
+ *            device-to-host copies and still one synchronisation.  Off, the step is what it was,
+ *            launch for launch.
+ *   i7m_ctrl_get_policy(h, K_out (G, n_k, 6, 13), xu_ref_out (G, n_k, 18))   a host copy from the
+ *            staging of the last step; either pointer may be NULL.  K_out as i7m_qp_policy's
+ *            ([K_k | kff_k]); xu_ref_out[g, k] = [x_k (12), u_k (6)].  Refused with the policy off or
+ *            when no step has run since it was turned on.
+ *   i7m_ctrl_set_applied(h, u_applied (G, 6))   a caller that applies the feedback itself reports
+ *            the time-average torque it applied since the last measurement; it replaces u_last for
+ *            the NEXT step's scoring only (that step's select stores its own control again).
+ *            Without it the feedback torque that fights the unknown force is invisible to the
+ *            estimator.  Entries finite; refused before a step or an x0 has set x_last.  One small
+ *            host-to-device copy on the handle's stream.
+ * All three: I7M_EINVAL with the argument named, before any device work, without an open session
+ * or on a bad argument.  Box-mode gains are out of scope (the session refuses I7M_QP_BOX).
  *
  * i7m_ctrl_end copies out the final XU_best (G, T) and hypotheses (G H, 6) (each may be NULL) and
  * closes the session; the final hypotheses stay the handle's external wrench in opts->frame, as
@@ -657,8 +707,9 @@ int i7m_mpc_run_tracking_multirate(i7m_handle* h, int32_t G, int32_t H, const do
  * solver state are refused ("controller session open"): i7m_solve, i7m_solve_device, i7m_qp,
  * i7m_qp_value, i7m_qp_policy, i7m_linearize, i7m_merit, i7m_linesearch, the six i7m_mpc_run*,
  * i7m_set_external_wrench, i7m_reset, i7m_admm_reset, i7m_set_stream.  The getters, the timing
- * calls, i7m_synchronize and the query hooks (i7m_eepos, i7m_aba, i7m_aba_derivatives, i7m_rk4:
- * they use scratch the session does not rely on between steps) stay available. */
+ * calls, i7m_synchronize, i7m_ctrl_set_policy / i7m_ctrl_get_policy / i7m_ctrl_set_applied and the
+ * query hooks (i7m_eepos, i7m_aba, i7m_aba_derivatives, i7m_rk4: they use scratch the session does
+ * not rely on between steps) stay available. */
 int i7m_ctrl_begin(i7m_handle* h, int32_t G, int32_t H, const double* x0 /* (G,12) or NULL */, const double* ref,
                    int32_t L, int32_t ref_stride, const int32_t* ref_phase /* (G) or NULL */,
                    const double* fhyp /* (G H,6) */, const i7m_sampled_opts* opts, double* u_out /* (G,6) or NULL */);
@@ -666,6 +717,9 @@ int i7m_ctrl_step(i7m_handle* h, const double* x_meas /* (G,12) */, double elaps
                   const double* noise /* (G H,3) or NULL */, double* u_out /* (G,6) */, int32_t* best_out /* (G) */,
                   double* fbest_out /* (G,6) */, double* err_out /* (G) */, double* ee_out /* (G,3) */);
 int i7m_ctrl_end(i7m_handle* h, double* xu_best_out /* (G,T) or NULL */, double* fhyp_out /* (G H,6) or NULL */);
+int i7m_ctrl_set_policy(i7m_handle* h, int32_t n_k);
+int i7m_ctrl_get_policy(i7m_handle* h, double* K_out /* (G,n_k,6,13) or NULL */, double* xu_ref_out /* (G,n_k,18) or NULL */);
+int i7m_ctrl_set_applied(i7m_handle* h, const double* u_applied /* (G,6) */);
 
 /* Per-kernel device timing with HIP events on the launch stream. */
 enum { I7M_K_LIN = 0, I7M_K_RICCATI = 1, I7M_K_LINESEARCH = 2, I7M_K_RICCATI_BOX = 3, I7M_K_IPM = 4, I7M_K_IPM_FUSED = 5,

@@ -20,7 +20,7 @@ import numpy as np
 LIB_DIR = os.path.join(os.path.dirname(os.path.abspath(__file__)), "lib")
 LIB_PATH = os.environ.get("I7M_LIB", os.path.join(LIB_DIR, "libindy7mpc.so"))  # I7M_LIB: A/B builds
 
-ABI_VERSION = 11  # I7M_ABI_VERSION of include/indy7_mpc.h this binding's SIGNATURES follow
+ABI_VERSION = 12  # I7M_ABI_VERSION of include/indy7_mpc.h this binding's SIGNATURES follow
 NJ, NX, NU = 6, 12, 6
 MAX_SQP = 8
 MAX_N = 64
@@ -135,7 +135,7 @@ class i7m_sampled_opts(C.Structure):
 class i7m_sampled_multirate_opts(C.Structure):
     _fields_ = i7m_sampled_opts._fields_ + [
         ("shift_warm_start", C.c_int32),
-        ("pad", C.c_int32),
+        ("control_from", C.c_int32),
     ]
 
 
@@ -206,6 +206,9 @@ SIGNATURES = [
                                  C.POINTER(i7m_sampled_opts), _DP]),
     ("i7m_ctrl_step", C.c_int, [_H, _DP, C.c_double, C.c_int32, _DP, _DP, _IP32, _DP, _DP, _DP]),
     ("i7m_ctrl_end", C.c_int, [_H, _DP, _DP]),
+    ("i7m_ctrl_set_policy", C.c_int, [_H, C.c_int32]),
+    ("i7m_ctrl_get_policy", C.c_int, [_H, _DP, _DP]),
+    ("i7m_ctrl_set_applied", C.c_int, [_H, _DP]),
     ("i7m_set_timing", C.c_int, [_H, C.c_int]),
     ("i7m_get_kernel_times", C.c_int, [_H, _DP, C.POINTER(C.c_int32), C.c_int32]),
     ("i7m_reset_kernel_times", C.c_int, [_H]),
@@ -643,13 +646,15 @@ class Handle:
                 raise ValueError(f"noise must be ({num_steps}, {G * Hn}, 3)")
         return xs, G, fh, Hn, fa, nz, self._opts(frame, reset_what, keep_best, decay, sim_dt, fa.shape[0])
 
-    def _multirate_opts(self, o, shift_warm_start):
-        """The multi-rate options struct from the family's (same fields first) and the shift flag."""
+    def _multirate_opts(self, o, shift_warm_start, control_from="new"):
+        """The multi-rate options struct from the family's (same fields first), the shift flag and
+        the plant's control ("new", "policy", or the C value: the library refuses the others)."""
         m = i7m_sampled_multirate_opts()
         _check(self._lib.i7m_sampled_multirate_opts_default(C.byref(m)))
         for f, _ in i7m_sampled_opts._fields_:
             setattr(m, f, getattr(o, f))
         m.shift_warm_start = int(shift_warm_start)
+        m.control_from = int(_CONTROLS.get(control_from, control_from))
         return m
 
     def _multirate_plan(self, sim_dt, num_steps):
@@ -663,7 +668,8 @@ class Handle:
         return n_sub.value, sub_start, shift
 
     def _run_family(self, xstart, num_steps, fhyp, f_actual, noise, sim_dt, frame, reset_what, keep_best, decay,
-                    endpoints=None, ref=None, ref_phase=None, ref_offset=None, shift_warm_start=None):
+                    endpoints=None, ref=None, ref_phase=None, ref_offset=None, shift_warm_start=None,
+                    control_from="new"):
         """The four loops of the family behind one marshalling: the goal source is `endpoints`, or
         `ref` with `ref_phase` and (single-rate plant) `ref_offset`; the plant is multi-rate where
         shift_warm_start is given.  The returned dict holds the entry point's outputs in the order of
@@ -683,7 +689,7 @@ class Handle:
         out = {"err" if track else "dist": np.empty((num_steps, G)), "best": np.empty((num_steps, G), dtype=np.int32),
                "q": np.empty((num_steps, G, NJ))}
         if multi:
-            o = self._multirate_opts(o, shift_warm_start)
+            o = self._multirate_opts(o, shift_warm_start, control_from)
             n_sub, sub_start, shift = self._multirate_plan(sim_dt, num_steps)
             out.update(u=np.empty((num_steps, G, NU)), xpath=np.empty((n_sub, G, NJ)))
         if track:
@@ -725,25 +731,29 @@ class Handle:
 
     def mpc_run_sampled_multirate(self, xstart, endpoints, num_steps, fhyp, f_actual, noise=None, sim_dt=0.001,
                                   frame="world", reset_what=ADMM_RESET_ALL, keep_best=False, decay=1.0,
-                                  shift_warm_start=0):
+                                  shift_warm_start=0, control_from="new"):
         """mpc_run_sampled with a multi-rate plant (i7m_mpc_run_sampled_multirate): sim_dt is not
         bounded by dt, a plant step is split at knot boundaries, the hypotheses are scored by one rk4
         step of the whole sim_dt.  shift_warm_start=1 shifts the rows' warm start by the knots a step
         completes.  Returns mpc_run_sampled's dict plus u (num_steps, G, 6) the control applied at
         each step, xpath (n_sub, G, 6) one q per plant sub-step, and the schedule: sub_start
-        (num_steps + 1,), shift (num_steps,)."""
+        (num_steps + 1,), shift (num_steps,).
+        control_from="policy": the plant runs under the winner's feedback policy, u_j + K_j (x - x_j)
+        per sub-step, and the hypotheses are scored by replaying the step under the recorded controls;
+        u stays the nominal first control."""
         return self._run_family(xstart, int(num_steps), fhyp, f_actual, noise, sim_dt, frame, reset_what, keep_best, decay,
-                                endpoints=endpoints, shift_warm_start=shift_warm_start)
+                                endpoints=endpoints, shift_warm_start=shift_warm_start, control_from=control_from)
 
     def mpc_run_tracking_multirate(self, xstart, ref, num_steps, fhyp, f_actual, ref_phase=None, noise=None,
                                    sim_dt=0.02, frame="world", reset_what=ADMM_RESET_ALL, keep_best=False, decay=1.0,
-                                   shift_warm_start=0):
+                                   shift_warm_start=0, control_from="new"):
         """mpc_run_tracking with a multi-rate plant (i7m_mpc_run_tracking_multirate): the window's
         offset at step i is the number of knots the plant has completed by then (the notebook's
         eepos_offset), computed by the library.  Returns mpc_run_tracking's dict plus u, xpath, off
-        (num_steps,) int32 those offsets, sub_start and shift."""
+        (num_steps,) int32 those offsets, sub_start and shift.  control_from as
+        mpc_run_sampled_multirate's."""
         return self._run_family(xstart, int(num_steps), fhyp, f_actual, noise, sim_dt, frame, reset_what, keep_best, decay,
-                                ref=ref, ref_phase=ref_phase, shift_warm_start=shift_warm_start)
+                                ref=ref, ref_phase=ref_phase, shift_warm_start=shift_warm_start, control_from=control_from)
 
     # ---- the controller session (i7m_ctrl_begin / _step / _end) ----------------------------
     def ctrl_begin(self, ref, fhyp, x0=None, groups=None, ref_phase=None, frame="world", reset_what=ADMM_RESET_ALL,
@@ -765,6 +775,7 @@ class Handle:
         _check(self._lib.i7m_ctrl_begin(self._h, G, Hn, _ptr(xs), _ptr(rf), *rf.shape,
                                         _iptr(rp), _ptr(fh), C.byref(o), _ptr(u)))
         self._ctrl = (G, Hn)
+        self._ctrl_nk = 0
         return u
 
     def ctrl_step(self, x_meas, elapsed, ref_offset, noise=None):
@@ -785,6 +796,27 @@ class Handle:
                                        _iptr(out["best"]), _ptr(out["fbest"]), _ptr(out["err"]), _ptr(out["ee"])))
         return out
 
+    def ctrl_set_policy(self, n_k):
+        """Turn the session's policy on for the first n_k stages (i7m_ctrl_set_policy; 0: off)."""
+        _check(self._lib.i7m_ctrl_set_policy(self._h, int(n_k)))
+        self._ctrl_nk = int(n_k)
+
+    def ctrl_get_policy(self):
+        """The winner's policy of the last step (i7m_ctrl_get_policy).  Returns (K (G, n_k, 6, 13) =
+        [K_k | kff_k], xu_ref (G, n_k, 18) = [x_k, u_k] of XU_best)."""
+        G, _ = getattr(self, "_ctrl", None) or (0, 0)
+        n_k = getattr(self, "_ctrl_nk", 0) if getattr(self, "_ctrl", None) else 0
+        K, xu = np.empty((G, n_k, NU, NX + 1)), np.empty((G, n_k, NX + NU))
+        _check(self._lib.i7m_ctrl_get_policy(self._h, _ptr(K), _ptr(xu)))
+        return K, xu
+
+    def ctrl_set_applied(self, u_applied):
+        """Report the time-average torque (G, 6) applied since the last measurement
+        (i7m_ctrl_set_applied): it replaces u_last for the next step's scoring only."""
+        G, _ = getattr(self, "_ctrl", None) or (np.size(u_applied) // NU, 0)
+        ua = None if u_applied is None else _f64(u_applied).reshape(G, NU)
+        _check(self._lib.i7m_ctrl_set_applied(self._h, _ptr(ua)))
+
     def ctrl_end(self):
         """Close the session (i7m_ctrl_end).  Returns a dict: xu_best (G, T) the final XU_best, fhyp
         (G * H, 6) the final hypotheses (left set on the handle)."""
@@ -792,6 +824,7 @@ class Handle:
         out = dict(xu_best=np.empty((G, self.T)), fhyp=np.empty((G * Hn, 6)))
         _check(self._lib.i7m_ctrl_end(self._h, _ptr(out["xu_best"]), _ptr(out["fhyp"])))
         self._ctrl = None
+        self._ctrl_nk = 0
         return out
 
     # ---- timing --------------------------------------------------------------------------

@@ -29,6 +29,7 @@
 #include "i7m_mpc_multirate.h"
 #include "i7m_mpc_sampled_multirate.h"
 #include "i7m_mpc_policy.h"
+#include "i7m_mpc_sampled_policy.h"
 #include "i7m_plan.h"
 
 // Source hash of the tree this library was built from (__graft_entry__.build passes it), so
@@ -71,9 +72,17 @@ hipError_t i7m_launch_policy_gather(int B, int N, int n_k, hipStream_t s, const 
 hipError_t i7m_launch_multirate_policy_step(int n, hipStream_t s, const void* model, const void* args, const void* knots,
                                             const double* kbuf);
 
+// i7m_mpc_sampled_policy_tu.hip (k_sampled_multirate_policy_step, k_ctrl_policy_copy); args: const
+// SampledMultirateArgs*, knots: const PolicyKnots*
+hipError_t i7m_launch_sampled_multirate_policy_step(int ng, int H, hipStream_t s, const void* model, const void* args,
+                                                    const void* knots, const double* kbuf);
+hipError_t i7m_launch_ctrl_policy_copy(int G, int H, int N, int n_k, hipStream_t s, const int* best, const double* kbuf,
+                                       const double* xub, double* out);
+
 static_assert(sizeof(i7m_problem_stats) == sizeof(ProblemStats), "stats layout");
 static_assert(ADMM_RES_MAX_N == ARES_N, "i7m_plan.h: k_admm_iter_res's horizon");
 static_assert(POLICY_MAX_SUB == MULTIRATE_MAX_SUB, "i7m_mpc_policy.h: PolicyKnots holds one step's sub-steps");
+static_assert(CTRL_POLICY_REC == CTRL_POLICY_STAGE && POLICY_K == CTRL_POLICY_K, "i7m_plan.h: the session's policy record");
 
 namespace {
 
@@ -128,6 +137,12 @@ struct CtrlSession {
   i7m_sampled_opts o{};
   Carved dev, host;
   CtrlArgs a{};  // the launches' arguments, all but the step's own (elapsed, off, noise, have_last, initial)
+  // the winner's policy (i7m_ctrl_set_policy): n_k stages (0: off) of CTRL_POLICY_REC doubles per
+  // group, on the device and in pinned staging; pol_stepped: a step has filled the staging
+  int n_k = 0;
+  bool pol_stepped = false;
+  double *d_pol = nullptr, *h_pol = nullptr;
+  std::vector<double> u_applied;  // i7m_ctrl_set_applied's staging: alive until the session ends
 };
 
 struct i7m_handle {
@@ -302,7 +317,15 @@ bool dev_alloc(i7m_handle* h, P** p, size_t bytes) {
 
 // The controller session's two allocations back (i7m_ctrl_end, i7m_destroy); nothing queued may
 // still use them.
+void ctrl_policy_release(CtrlSession& c) {
+  if (c.d_pol) (void)hipFree(c.d_pol);
+  if (c.h_pol) (void)hipHostFree(c.h_pol);
+  c.d_pol = c.h_pol = nullptr;
+  c.n_k = 0;
+  c.pol_stepped = false;
+}
 void ctrl_release(i7m_handle* h) {
+  ctrl_policy_release(h->ctrl);
   h->ctrl.dev.release();
   h->ctrl.host.release();
   h->ctrl = CtrlSession{};
@@ -1898,7 +1921,7 @@ namespace {
 // options every kind shares (null: the defaults); shift_warm_start: the multi-rate kinds' flag.
 SampledCall describe_call(const i7m_handle* h, SampledKind kind, int G, int H, int num_steps, const i7m_sampled_opts* opts,
                           int shift_warm_start, const GoalSource& goal, const double* xstart, const double* fhyp,
-                          const double* f_actual, const double* hist_out) {
+                          const double* f_actual, const double* hist_out, int control_from = I7M_CONTROL_NEW) {
   SampledCall c;
   c.kind = kind;
   c.qp_mode = h->cfg.qp_mode;
@@ -1910,6 +1933,7 @@ SampledCall describe_call(const i7m_handle* h, SampledKind kind, int G, int H, i
   (void)i7m_sampled_opts_default(&c.o);
   if (opts) c.o = *opts;
   c.shift_warm_start = shift_warm_start;
+  c.control_from = control_from;
   c.goal = goal;
   c.xstart = xstart;
   c.fhyp = fhyp;
@@ -1951,6 +1975,7 @@ int sampled_loop(i7m_handle* h, const std::string& who, const SampledCall& c, co
   if (h->ctrl.open) return session_open();
   const int N = (int)h->N;
   const bool multi = multirate_kind(c.kind), track = tracking_kind(c.kind);
+  const bool policy = multi && c.control_from == I7M_CONTROL_POLICY;
   MultirateSchedule sch;
   int rc;
   if ((rc = check_call(who, c, N, &sch))) return rc;
@@ -2026,8 +2051,21 @@ int sampled_loop(i7m_handle* h, const std::string& who, const SampledCall& c, co
     a.ref_stride = gs.ref_stride;
     m.hist_stride = G;
     int rc3;
+    // I7M_CONTROL_POLICY: the gains of the solve just run, the QP at xu_new with x_0 = xs, on this
+    // range's rows and stream behind that solve and before the step launch: the rows' wrenches are
+    // still the ones the solve used (the select step resamples them afterwards), so row `best`'s
+    // slots of kbuf are the winner's policy
+    const Bufs W = bufs_at(h, lo);
+    const auto gains = [&]() -> int {
+      if (!policy) return I7M_OK;
+      const int r = policy_pass(h, s, W, params_of(h, n, 3), xu_new, xs, g);
+      if (r) return r;
+      if (h->policy_zero_k) HIPCHK(hipMemsetAsync(W.kbuf, 0, (size_t)n * (N - 1) * KBUF_STRIDE * 8, s));
+      return I7M_OK;
+    };
     if ((rc3 = loop_reset(h, lo, n, I7M_ADMM_RESET_ALL, s, d_rho0))) return rc3;
     if ((rc3 = run_sqp(h, n, xu, xu_new, xs, g, 3, nullptr, lo, s, mark))) return rc3;
+    if ((rc3 = gains())) return rc3;
     // launch i: select(i - 1) (i = 0: the initial solve's row 0), then plant(i) ... goal(i);
     // the last launch only selects
     for (int i = 0; i <= num_steps; ++i) {
@@ -2049,7 +2087,13 @@ int sampled_loop(i7m_handle* h, const std::string& who, const SampledCall& c, co
         m.sub_dt = d_sub + s0;
         m.u_out = d_u + cur * 6;
         m.xpath_out = d_xp + ((size_t)s0 * G + glo) * 6;
-        HIPCHK(i7m_launch_sampled_multirate_step(ng, H, s, h->d_model, &m));
+        if (policy) {
+          PolicyKnots kn{};
+          for (int e = 0; e < m.n_sub; ++e) kn.j[e] = (unsigned char)sch.sub_knot[s0 + e];
+          HIPCHK(i7m_launch_sampled_multirate_policy_step(ng, H, s, h->d_model, &m, &kn, W.kbuf));
+        } else {
+          HIPCHK(i7m_launch_sampled_multirate_step(ng, H, s, h->d_model, &m));
+        }
       } else {
         hipLaunchKernelGGL(k_sampled_step, dim3(ng), dim3((H + 63) / 64 * 64), 0, s, h->d_model, a);
         HIPCHK(hipGetLastError());
@@ -2057,6 +2101,7 @@ int sampled_loop(i7m_handle* h, const std::string& who, const SampledCall& c, co
       if (!a.plant) break;
       if ((rc3 = loop_reset(h, lo, n, o.reset_what, s, d_rho0))) return rc3;
       if ((rc3 = run_sqp(h, n, xu, xu_new, xs, g, 3, nullptr, lo, s))) return rc3;
+      if ((rc3 = gains())) return rc3;
     }
     return I7M_OK;
   }, stagger_cut_grouped(B, H));
@@ -2079,12 +2124,13 @@ int sampled_loop(i7m_handle* h, const std::string& who, const SampledCall& c, co
 // A multi-rate call's options as the family's shared ones and the shift flag (null: the defaults).
 struct SharedOpts {
   i7m_sampled_opts o;
-  int shift_warm_start = 0;
+  int shift_warm_start = 0, control_from = I7M_CONTROL_NEW;
   explicit SharedOpts(const i7m_sampled_multirate_opts* m) {
     (void)i7m_sampled_opts_default(&o);
     if (!m) return;
     o = i7m_sampled_opts{m->sim_dt, m->decay, m->frame, m->reset_what, m->keep_best, m->n_actual};
     shift_warm_start = m->shift_warm_start;
+    control_from = m->control_from;
   }
 };
 
@@ -2142,7 +2188,7 @@ int i7m_sampled_multirate_opts_default(i7m_sampled_multirate_opts* o) {
   o->keep_best = s.keep_best;
   o->n_actual = s.n_actual;
   o->shift_warm_start = 0;  // the reference's shift is commented out, src/gato_mpc_batch_sample.py:194-201
-  o->pad = 0;
+  o->control_from = I7M_CONTROL_NEW;
   return I7M_OK;
 }
 
@@ -2154,7 +2200,8 @@ int i7m_mpc_run_sampled_multirate(i7m_handle* h, int32_t G, int32_t H, const dou
   if (!h) return fail(I7M_EINVAL, "null handle");
   const SharedOpts so(opts);
   const SampledCall c = describe_call(h, SampledKind::endpoints_multirate, G, H, num_steps, &so.o, so.shift_warm_start,
-                                      GoalSource::of_endpoints(endpoints, n_endpoints), xstart, fhyp, f_actual, dist_out);
+                                      GoalSource::of_endpoints(endpoints, n_endpoints), xstart, fhyp, f_actual, dist_out,
+                                      so.control_from);
   SampledOut out;
   out.hist = dist_out;
   out.best = best_out;
@@ -2178,7 +2225,7 @@ int i7m_mpc_run_tracking_multirate(i7m_handle* h, int32_t G, int32_t H, const do
   const SharedOpts so(opts);
   const SampledCall c = describe_call(h, SampledKind::tracking_multirate, G, H, num_steps, &so.o, so.shift_warm_start,
                                       GoalSource::of_reference(ref, L, ref_stride, ref_phase, nullptr), xstart, fhyp,
-                                      f_actual, err_out);
+                                      f_actual, err_out, so.control_from);
   SampledOut out;
   out.hist = err_out;
   out.best = best_out;
@@ -2333,11 +2380,19 @@ int i7m_ctrl_step(i7m_handle* h, const double* x_meas, double elapsed, int32_t r
   hipLaunchKernelGGL(k_ctrl_measure, dim3(c.G), dim3((c.H + 63) / 64 * 64), 0, h->stream, h->d_model, a);
   HIPCHK(hipGetLastError());
   if ((rc = ctrl_solve(h, c.o.reset_what))) return rc;
+  // the policy on: the gains of every row behind the solve, while the rows' wrenches are the solve's
+  if (c.n_k > 0 && (rc = policy_pass(h, h->stream, bufs_at(h, 0), params_of(h, (int)B, 3), h->d_out, h->d_xs, h->d_goal)))
+    return rc;
   ctrl_launch_select(h, a);
   HIPCHK(hipGetLastError());
+  if (c.n_k > 0) {
+    HIPCHK(i7m_launch_ctrl_policy_copy(c.G, c.H, (int)h->N, c.n_k, h->stream, a.best, h->d_kbuf, a.xub, c.d_pol));
+    if ((rc = copy_out(h, c.h_pol, c.d_pol, G * c.n_k * CTRL_POLICY_REC))) return rc;
+  }
   if ((rc = copy_out(h, pr, a.rec, G * CTRL_REC))) return rc;
   HIPCHK(hipStreamSynchronize(h->stream));
   c.have_last = true;
+  c.pol_stepped = c.n_k > 0;
   for (size_t g = 0; g < G; ++g) {
     const double* r = pr + g * CTRL_REC;
     for (int k = 0; k < 6; ++k) u_out[6 * g + k] = r[CREC_U + k];
@@ -2347,6 +2402,66 @@ int i7m_ctrl_step(i7m_handle* h, const double* x_meas, double elapsed, int32_t r
     for (int k = 0; ee_out && k < 3; ++k) ee_out[3 * g + k] = r[CREC_EE + k];
   }
   return I7M_OK;
+}
+
+int i7m_ctrl_set_policy(i7m_handle* h, int32_t n_k) {
+  const std::string who = "ctrl_set_policy";
+  if (!h) return fail(I7M_EINVAL, "null handle");
+  CtrlSession& c = h->ctrl;
+  const char* which = "";
+  long at = 0;
+  if (!ctrl_set_policy_ok(c.open, n_k, (int)h->N, &which, &at)) return fail(I7M_EINVAL, ctrl_policy_refusal(who, which, at, (int)h->N));
+  HIPCHK(hipSetDevice(h->dev));
+  HIPCHK(hipStreamSynchronize(h->stream));  // nothing queued still uses the old buffers
+  ctrl_policy_release(c);
+  if (n_k == 0 || c.G == 0) {
+    c.n_k = n_k;
+    return I7M_OK;
+  }
+  const size_t bytes = 8 * (size_t)c.G * n_k * CTRL_POLICY_REC;
+  if (hipMalloc((void**)&c.d_pol, bytes) != hipSuccess) {
+    c.d_pol = nullptr;
+    return fail(I7M_ENOMEM, who + ": device allocation failed");
+  }
+  if (hipHostMalloc((void**)&c.h_pol, bytes, hipHostMallocDefault) != hipSuccess) {
+    c.h_pol = nullptr;
+    ctrl_policy_release(c);
+    return fail(I7M_ENOMEM, who + ": pinned host allocation failed");
+  }
+  c.n_k = n_k;
+  return I7M_OK;
+}
+
+int i7m_ctrl_get_policy(i7m_handle* h, double* K_out, double* xu_ref_out) {
+  const std::string who = "ctrl_get_policy";
+  if (!h) return fail(I7M_EINVAL, "null handle");
+  const CtrlSession& c = h->ctrl;
+  const char* which = "";
+  long at = 0;
+  if (!ctrl_get_policy_ok(c.open, c.n_k > 0, c.pol_stepped || (c.n_k > 0 && c.G == 0), &which, &at))
+    return fail(I7M_EINVAL, ctrl_policy_refusal(who, which, at, (int)h->N));
+  // the staging of the last step, whose synchronisation has passed: a host copy
+  for (size_t e = 0; e < (size_t)c.G * c.n_k; ++e) {
+    const double* r = c.h_pol + e * CTRL_POLICY_REC;
+    if (K_out) std::memcpy(K_out + e * CTRL_POLICY_K, r, 8 * CTRL_POLICY_K);
+    if (xu_ref_out) std::memcpy(xu_ref_out + e * CTRL_POLICY_XU, r + CTRL_POLICY_K, 8 * CTRL_POLICY_XU);
+  }
+  return I7M_OK;
+}
+
+int i7m_ctrl_set_applied(i7m_handle* h, const double* u_applied) {
+  const std::string who = "ctrl_set_applied";
+  if (!h) return fail(I7M_EINVAL, "null handle");
+  CtrlSession& c = h->ctrl;
+  const char* which = "";
+  long at = 0;
+  if (!ctrl_set_applied_ok(c.open, c.have_last, u_applied, c.G, &which, &at))
+    return fail(I7M_EINVAL, ctrl_policy_refusal(who, which, at, (int)h->N));
+  if (c.G == 0) return I7M_OK;
+  HIPCHK(hipSetDevice(h->dev));
+  // u_last of the next step's scoring; that step's select stores its own control over it
+  c.u_applied.assign(u_applied, u_applied + 6 * (size_t)c.G);
+  return copy_in(h, c.a.u_last, c.u_applied.data(), 6 * (size_t)c.G);
 }
 
 int i7m_ctrl_end(i7m_handle* h, double* xu_best_out, double* fhyp_out) {

@@ -485,6 +485,7 @@ struct SampledCall {
   int G = 0, H = 0, num_steps = 0;
   i7m_sampled_opts o{};
   int shift_warm_start = 0;  // the multi-rate kinds only
+  int control_from = I7M_CONTROL_NEW;  // or, the multi-rate kinds only, I7M_CONTROL_POLICY
   GoalSource goal;
   const double *xstart = nullptr, *fhyp = nullptr, *f_actual = nullptr;
   const double* hist_out = nullptr;
@@ -507,6 +508,8 @@ inline bool sampled_call_ok(const SampledCall& c, const char** which, long* at) 
   if (loop && !multi && (!(c.o.sim_dt > 0.0) || !(c.o.sim_dt <= c.dt))) return no("sim_dt", 0);
   if (multi && (!std::isfinite(c.o.sim_dt) || !(c.o.sim_dt > 0.0))) return no("sim_dt", 0);
   if (multi && c.shift_warm_start != 0 && c.shift_warm_start != 1) return no("shift_warm_start", c.shift_warm_start);
+  // the policy-driven plant is the multi-rate kinds' alone; I7M_CONTROL_PREV (1) has no variant here
+  if (c.control_from != I7M_CONTROL_NEW && !(multi && c.control_from == I7M_CONTROL_POLICY)) return no("control_from", c.control_from);
   if (c.o.frame != I7M_WRENCH_LOCAL && c.o.frame != I7M_WRENCH_WORLD) return no("frame", c.o.frame);
   if (c.o.reset_what & ~I7M_ADMM_RESET_ALL) return no("reset_what", c.o.reset_what);
   if (!track && g.n_endpoints < 1) return no("n_endpoints", g.n_endpoints);
@@ -541,6 +544,8 @@ inline std::string sampled_refusal(const std::string& who, const std::string& wh
   if (which == "L") return who + ": L = " + v + ", the reference needs >= 1 point";
   if (which == "ref_stride") return who + ": ref_stride = " + v + " is not 3 or 6";
   if (which == "n_actual") return who + ": n_actual must be 1 or num_steps";
+  if (which == "control_from")
+    return who + ": control_from = " + v + " is not I7M_CONTROL_NEW (0) or, for a multi-rate loop, I7M_CONTROL_POLICY (2)";
   if (which == "ref_offset" && at < 0) return who + ": null ref_offset with num_steps > 0";
   if (which == "ref_phase" || which == "ref_offset") return who + ": " + which + "[" + v + "] is negative";
   return who + ": null " + which;
@@ -549,7 +554,9 @@ inline std::string sampled_refusal(const std::string& who, const std::string& wh
 // The multi-rate kinds' check: the family's (sampled_call_ok with a multi-rate kind: everything it
 // refuses for the single-rate loops but sim_dt > dt, and shift_warm_start), then the plant's
 // schedule for the handle's horizon N (multirate_schedule: *which = "shift" or "substeps", *at the
-// step).  On success *sch is the schedule the loop runs.
+// step), then under control_from = I7M_CONTROL_POLICY the N - 2 bound of i7m_mpc_run_multirate
+// (multirate_policy_bad_step: *which = "policy_shift", *at the step).  On success *sch is the schedule
+// the loop runs.
 inline bool sampled_multirate_call_ok(const SampledCall& c, int N, MultirateSchedule* sch, const char** which, long* at) {
   *sch = MultirateSchedule{};
   if (!multirate_kind(c.kind)) {
@@ -558,12 +565,19 @@ inline bool sampled_multirate_call_ok(const SampledCall& c, int N, MultirateSche
     return false;
   }
   if (!sampled_call_ok(c, which, at)) return false;
-  return multirate_schedule(c.dt, c.o.sim_dt, N, c.num_steps, sch, which, at);
+  if (!multirate_schedule(c.dt, c.o.sim_dt, N, c.num_steps, sch, which, at)) return false;
+  if (c.control_from == I7M_CONTROL_POLICY && (*at = multirate_policy_bad_step(*sch, N)) >= 0) {
+    *sch = MultirateSchedule{};
+    *which = "policy_shift";
+    return false;
+  }
+  return true;
 }
 // The text of a refusal by sampled_multirate_call_ok, for the entry point `who`.
 inline std::string sampled_multirate_refusal(const std::string& who, const std::string& which, long at,
                                              const SampledCall& c, int N) {
   if (which == "sim_dt" || which == "shift" || which == "substeps") return multirate_refusal(who, which, at, c.o.sim_dt, N);
+  if (which == "policy_shift") return multirate_policy_refusal(who, at, c.o.sim_dt, N);
   if (which == "shift_warm_start") return who + ": shift_warm_start = " + std::to_string(at) + " is not 0 or 1";
   if (which == "kind") return who + ": not a multi-rate call";
   return sampled_refusal(who, which, at, c.max_batch);
@@ -628,6 +642,50 @@ inline std::string ctrl_step_refusal(const std::string& who, const std::string& 
   if (which == "elapsed") return who + ": elapsed must be finite and > 0";
   if (which == "ref_offset") return who + ": ref_offset = " + v + " is negative";
   if (which == "x_meas" && at >= 0) return who + ": x_meas[" + v + "] is not finite";
+  return who + ": null " + which;
+}
+
+
+// ---- the controller session's policy (i7m_ctrl_set_policy / _get_policy / _set_applied) ----------
+
+// One group's stage of the session's policy buffer: K~_k (6 x 13), then [x_k, u_k] of XU_best.
+constexpr int CTRL_POLICY_K = 78, CTRL_POLICY_XU = 18, CTRL_POLICY_STAGE = CTRL_POLICY_K + CTRL_POLICY_XU;
+// The three calls' argument checks, host reads only; `open`: a session is open.  *which names the
+// argument ("session": none is open), *at the offending value or entry (-1: a null pointer).
+inline bool ctrl_set_policy_ok(bool open, int n_k, int N, const char** which, long* at) {
+  *which = !open ? "session" : "n_k";
+  *at = n_k;
+  return open && n_k >= 0 && n_k <= N - 1;
+}
+// on: n_k > 0; stepped: a step has run since the policy was turned on
+inline bool ctrl_get_policy_ok(bool open, bool on, bool stepped, const char** which, long* at) {
+  *which = !open ? "session" : !on ? "off" : "step";
+  *at = 0;
+  return open && on && stepped;
+}
+// have_last: a step or an x0 has set x_last
+inline bool ctrl_set_applied_ok(bool open, bool have_last, const double* u_applied, int G, const char** which, long* at) {
+  const auto no = [&](const char* w, long a) {
+    *which = w;
+    *at = a;
+    return false;
+  };
+  if (!open) return no("session", 0);
+  if (!u_applied) return no("u_applied", -1);
+  if (!have_last) return no("x_last", 0);
+  for (long e = 0; e < 6L * G; ++e)
+    if (!std::isfinite(u_applied[e])) return no("u_applied", e);
+  return true;
+}
+// The text of a refusal by one of the three.
+inline std::string ctrl_policy_refusal(const std::string& who, const std::string& which, long at, int N) {
+  const std::string v = std::to_string(at);
+  if (which == "session") return who + ": no controller session is open on this handle (i7m_ctrl_begin)";
+  if (which == "n_k") return who + ": n_k = " + v + " outside [0, N - 1 = " + std::to_string(N - 1) + "]";
+  if (which == "off") return who + ": the session's policy is off (i7m_ctrl_set_policy with n_k > 0)";
+  if (which == "step") return who + ": no i7m_ctrl_step has run since the policy was turned on";
+  if (which == "x_last") return who + ": no x_last yet (a step, or i7m_ctrl_begin with x0, sets it): nothing to score u_applied against";
+  if (which == "u_applied" && at >= 0) return who + ": u_applied[" + v + "] is not finite";
   return who + ": null " + which;
 }
 

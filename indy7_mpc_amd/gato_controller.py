@@ -38,7 +38,7 @@ from .model import default_model
 
 class GATO_Controller:
     def __init__(self, ref_traj=None, batch_size=1, N=32, dt=0.01, f_ext_std=0.0, f_ext_resample_std=0.0, model=None,
-                 seed=None, qp_mode="admm", groups=1, device_id=0):
+                 seed=None, qp_mode="admm", groups=1, device_id=0, policy_knots=0):
         if ref_traj is None:
             raise ValueError("ref_traj must be provided")
         mode = _sampling.qp_mode_of(batch_size, qp_mode)
@@ -57,15 +57,23 @@ class GATO_Controller:
         self._h.ctrl_begin(ref, np.tile(self.f_ext_batch, (self.groups, 1)), x0=None, groups=self.groups, frame="world",
                            reset_what=_lib.ADMM_RESET_ALL, keep_best=True, decay=0.97)
         self._open = True
+        # the winner's feedback policy for a torque loop faster than the solver (policy(), control())
+        self.policy_knots = int(policy_knots)
+        self._policy = None
+        if self.policy_knots:
+            self._h.ctrl_set_policy(self.policy_knots)
         # stats (:188-193), one entry per step
         self.dts, self.tracking_errors, self.ee_positions, self.ee_ref_positions = [], [], [], []
         self.joint_positions, self.solve_times, self.best_ids, self.f_ext_best = [], [], [], []
         self.last_time = time.time()
 
-    def step(self, x_curr, elapsed_time=None):
+    def step(self, x_curr, elapsed_time=None, u_applied=None):
         """joint_callback (:201-250) on the measured state x_curr (12,) (or (groups, 12)):
         elapsed_time seconds since the previous state, None = the wall clock since the previous
-        call (:209-211).  Returns u_curr (6,) (or (groups, 6)), the torques to command."""
+        call (:209-211).  u_applied (6,) (or (groups, 6)): the time-average torque a caller that
+        applies control() itself has applied since the previous state; the hypotheses are scored
+        against it instead of the last returned torque.  Returns u_curr (6,) (or (groups, 6)), the
+        torques to command."""
         now = time.time()
         elapsed = now - self.last_time if elapsed_time is None else float(elapsed_time)
         x = np.asarray(x_curr, float).reshape(self.groups, self.nx)
@@ -74,7 +82,10 @@ class GATO_Controller:
         if self.resample_f_ext:
             noise = _sampling.resampling_noise(self.rng, self.f_ext_resample_std, self.groups * self.batch_size)
         t0 = time.perf_counter()
+        if u_applied is not None:
+            self._h.ctrl_set_applied(np.asarray(u_applied, float).reshape(self.groups, self.nu))
         r = self._h.ctrl_step(x, elapsed, offset, noise=noise)
+        self._policy = None
         solve_time = time.perf_counter() - t0
         # a refused step (a non-finite state, a clock that did not advance) changes nothing above
         self.last_time = now
@@ -90,6 +101,26 @@ class GATO_Controller:
         self.best_ids.append(int(r["best"][0]) if one else r["best"])
         self.f_ext_best.append(r["fbest"][0] if one else r["fbest"])
         return r["u"][0] if one else r["u"]
+
+    def policy(self):
+        """The winner's feedback policy of the last step (policy_knots > 0): a dict of K
+        (G, n_k, 6, 12), kff (G, n_k, 6), x_ref (G, n_k, 12) and u_ref (G, n_k, 6), knot k at time
+        k dt after the measurement the step was given."""
+        if self._policy is None:
+            K, xu = self._h.ctrl_get_policy()
+            self._policy = {"K": K[..., :12].copy(), "kff": K[..., 12].copy(), "x_ref": xu[..., :12].copy(),
+                            "u_ref": xu[..., 12:].copy()}
+        return self._policy
+
+    def control(self, x, t):
+        """The torque a loop faster than the solver applies at state x (12,) (or (groups, 12)), t
+        seconds after the last step's measurement: u_ref[j] + K[j] (x - x_ref[j]) with
+        j = min(int(t / dt), n_k - 1).  Plain numpy on the last step's policy."""
+        p = self.policy()
+        j = min(int(t / self.dt), self.policy_knots - 1)
+        dx = np.asarray(x, float).reshape(self.groups, self.nx) - p["x_ref"][:, j]
+        u = p["u_ref"][:, j] + np.einsum("grc,gc->gr", p["K"][:, j], dx)
+        return u[0] if self.groups == 1 else u
 
     def get_stats(self):
         return {k: getattr(self, k) for k in ("dts", "tracking_errors", "ee_positions", "ee_ref_positions",

@@ -135,18 +135,19 @@ class MPC_GATO_Batch_Sample:
             noise = _sampling.resampling_noise(self.rng, self.f_ext_resample_std, num_steps, G * self.batch_size)
         return fa, noise, self._handle(G * self.batch_size)
 
-    def run_mpc_groups(self, xstarts, endpoints, sim_dt=0.001, sim_time=5, f_actual=None):
+    def run_mpc_groups(self, xstarts, endpoints, sim_dt=0.001, sim_time=5, f_actual=None, feedback=False):
         """G independent controllers, one per row of xstarts (G, 12), each with this object's
         hypotheses and its own resampling noise.  f_actual: (6,), (G, 6) or (num_steps, G, 6)
         world-frame wrenches (default: constant_f_ext for every group).  Returns (xpaths, stats): a
         list of G q-paths, and the reference's stats keys with a (logged steps, G) layout, plus
-        'best_ids' and 'f_ext_best' (every step)."""
+        'best_ids' and 'f_ext_best' (every step).  feedback=True: the plant runs under the winner's
+        feedback policy (control_from="policy"), through the multi-rate loop whatever sim_dt is."""
         xs = np.asarray(xstarts, float).reshape(-1, 12)
         G, H = xs.shape[0], self.batch_size
         num_steps = int(sim_time / sim_dt)
         fa, noise, h = self._run_inputs(G, num_steps, f_actual)
-        if sim_dt > self.dt:
-            return self._run_mpc_groups_multirate(h, xs, endpoints, num_steps, fa, noise, sim_dt)
+        if sim_dt > self.dt or feedback:
+            return self._run_mpc_groups_multirate(h, xs, endpoints, num_steps, fa, noise, sim_dt, feedback)
         t0 = time.perf_counter()
         r = h.mpc_run_sampled(xs, endpoints, num_steps, np.tile(self.f_ext_batch, (G, 1)), fa, noise=noise,
                               sim_dt=sim_dt, frame="world", reset_what=_lib.ADMM_RESET_ALL, keep_best=self.keep_best,
@@ -168,14 +169,15 @@ class MPC_GATO_Batch_Sample:
         self.last = r
         return xpaths, stats
 
-    def _run_mpc_groups_multirate(self, h, xs, endpoints, num_steps, fa, noise, sim_dt):
+    def _run_mpc_groups_multirate(self, h, xs, endpoints, num_steps, fa, noise, sim_dt, feedback=False):
         """run_mpc_groups with sim_dt > dt (i7m_mpc_run_sampled_multirate): the paths hold one q per
         plant sub-step, control_inputs (logged, G, 6) one control per logged step."""
         G, H = xs.shape[0], self.batch_size
         t0 = time.perf_counter()
         r = h.mpc_run_sampled_multirate(xs, endpoints, num_steps, np.tile(self.f_ext_batch, (G, 1)), fa, noise=noise,
                                         sim_dt=sim_dt, frame="world", reset_what=_lib.ADMM_RESET_ALL,
-                                        keep_best=self.keep_best, decay=self.decay)
+                                        keep_best=self.keep_best, decay=self.decay,
+                                        control_from="policy" if feedback else "new")
         per_step = (time.perf_counter() - t0) / max(num_steps, 1)
         self.f_ext_batch = r["fhyp"][:H].copy()
         ran = np.isfinite(r["xpath"][:, :, 0])  # a group's path ends with the step it stopped at
@@ -191,7 +193,8 @@ class MPC_GATO_Batch_Sample:
         self.last = r
         return xpaths, stats
 
-    def run_fig8_groups(self, xstarts, fig8_traj, sim_dt=0.001, sim_time=5, f_actual=None, ref_phase=None):
+    def run_fig8_groups(self, xstarts, fig8_traj, sim_dt=0.001, sim_time=5, f_actual=None, ref_phase=None,
+                        feedback=False):
         """G independent controllers on the notebook's figure-8 run (i7m_mpc_run_tracking_multirate),
         one per row of xstarts (G, 12), group g starting at point ref_phase[g] of the reference
         (default 0).  fig8_traj: flat with six entries per point (as the notebook's figure8 builds
@@ -200,7 +203,8 @@ class MPC_GATO_Batch_Sample:
         the paths, and it is not logged.  Returns (xpaths, stats): a list of G q-paths, one q per
         plant sub-step, and the notebook's stats keys with a (logged steps, G) layout
         (goal_distances (logged, G), control_inputs (logged, G, 6)) plus 'best_ids', 'f_ext_best'
-        and 'offsets' (every step)."""
+        and 'offsets' (every step).  feedback=True: the plant runs under the winner's feedback policy
+        (control_from="policy"); control_inputs stay the nominal controls."""
         xs = np.asarray(xstarts, float).reshape(-1, 12)
         G, H = xs.shape[0], self.batch_size
         ref = _sampling.reference_points(fig8_traj)
@@ -210,7 +214,8 @@ class MPC_GATO_Batch_Sample:
         t0 = time.perf_counter()
         r = h.mpc_run_tracking_multirate(xs, ref, num_steps, np.tile(self.f_ext_batch, (G, 1)), fa, ref_phase=phase,
                                          noise=noise, sim_dt=sim_dt, frame="world", reset_what=_lib.ADMM_RESET_ALL,
-                                         keep_best=self.keep_best, decay=self.decay)
+                                         keep_best=self.keep_best, decay=self.decay,
+                                         control_from="policy" if feedback else "new")
         per_step = (time.perf_counter() - t0) / max(num_steps, 1)
         self.f_ext_batch = r["fhyp"][:H].copy()
         xpaths = [[q for q in r["xpath"][:, g]] for g in range(G)]
@@ -226,10 +231,11 @@ class MPC_GATO_Batch_Sample:
         self.last = r
         return xpaths, stats
 
-    def run_mpc_fig8(self, xstart, fig8_traj, sim_dt=0.001, sim_time=5):
+    def run_mpc_fig8(self, xstart, fig8_traj, sim_dt=0.001, sim_time=5, feedback=False):
         """One controller, as the notebook's run_mpc_fig8: (xpath, stats), xpath one q per plant
         sub-step, the stats logged where abs((i * sim_dt) % 0.05) < 1e-5."""
-        xpaths, st = self.run_fig8_groups(np.asarray(xstart, float).reshape(1, 12), fig8_traj, sim_dt, sim_time)
+        xpaths, st = self.run_fig8_groups(np.asarray(xstart, float).reshape(1, 12), fig8_traj, sim_dt, sim_time,
+                                          feedback=feedback)
         self.xpath += xpaths[0]
         stats = {
             "solve_times": st["solve_times"],
@@ -284,13 +290,14 @@ class MPC_GATO_Batch_Sample:
         st = self.run_tracking_groups(np.asarray(xstart, float).reshape(1, 12), ref_traj, sim_dt, sim_time, f_actual)
         return {k: (v if k == "solve_times" else v[:, 0]) for k, v in st.items()}
 
-    def run_mpc(self, xstart, endpoints, sim_dt=0.001, sim_time=5):
+    def run_mpc(self, xstart, endpoints, sim_dt=0.001, sim_time=5, feedback=False):
         """One controller, as the reference's run_mpc (src/gato_mpc_batch_sample.py:106-252):
         (xpath, stats), xpath one q per control step (sim_dt > dt: per plant sub-step) until the
         final goal is reached."""
-        xpaths, st = self.run_mpc_groups(np.asarray(xstart, float).reshape(1, 12), endpoints, sim_dt, sim_time)
+        xpaths, st = self.run_mpc_groups(np.asarray(xstart, float).reshape(1, 12), endpoints, sim_dt, sim_time,
+                                         feedback=feedback)
         self.xpath += xpaths[0]
-        if sim_dt > self.dt:
+        if sim_dt > self.dt or feedback:
             keep = np.isfinite(st["goal_distances"][:, 0])
             controls = [u for u in st["control_inputs"][keep, 0]]
         else:
